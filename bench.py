@@ -11,8 +11,24 @@ Default workload (BASELINE.json configs[1]/[2]): k=16, m=4, 1024 objects of
 (torchrun), objects round-robin by rank, no data-path collective ("weak"
 scaling: per-GPU work is fixed).  rank 0 prints ONE JSON line.
 
+A plain run does what the headline needs and no more: it sets up, warms up
+(loading the survivor set's own restore kernel), checks the restored objects
+against the inputs on the device, times the K steps and prints the line
+(`value`, `ms_per_step`, the per-kernel times of those same steps and the
+roofline block derived from them).  `--full` adds every leg reported beside
+the metric, each a run of its own: the AOT repair, regenerate, the SHA-256
+replica names, the 16-byte stride, the k=32/m=8 leg (C4), the live shape and
+the CPU baseline; the `--no-*` switches drop single legs of a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step computed, the replicas
+and the restored objects, as DIR/<name>.npy (float32).  The inputs depend on
+the arguments alone, so two builds can be compared output for output.  An
+output of more than DUMP_SAMPLES bytes is dumped as a fixed, seeded sample of
+its bytes (the same positions in every run with the same arguments).
+
   python bench.py [--gpus N] [--steps K] [--warmup W] [--k 16] [--m 4]
-                  [--objects 1024] [--object-mib 64] [--no-cpu-baseline]
+                  [--objects 1024] [--object-mib 64] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-live] [--no-c4] [--no-align16]]
 """
 from __future__ import annotations
 
@@ -28,6 +44,9 @@ sys.path.insert(0, ROOT)
 
 SEED = 0x7664730000000000
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_SEED = 0x64756D70
+DUMP_SAMPLES = 6_000_000  # bytes sampled per dumped output: 2 x 24 MB of float32, under the 64 MB a dump may take
+DUMP_EDGE = 4096          # and the first / last bytes of each, dumped whole
 
 
 def parse():
@@ -40,6 +59,11 @@ def parse():
     p.add_argument("--objects", type=int, default=1024, help="objects per GPU")
     p.add_argument("--object-mib", type=float, default=64.0)
     p.add_argument("--erase", type=str, default="", help="comma list of erased replica ids")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs reported beside the metric (AOT repair, regenerate, SHA-256, 16-byte "
+                        "stride, C4, live shape, CPU baseline); off: only the headline's timed steps")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the replicas and restored objects of the last timed step as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-live", action="store_true", help="skip the live-shape line (k=32, n=64, 64 KiB objects)")
     p.add_argument("--no-align16", action="store_true", help="skip the 16-byte replica stride line")
@@ -194,6 +218,47 @@ def max_over_ranks(values, dist, device):
     t = torch.tensor(list(values), dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return [float(x) for x in t.tolist()]
+
+
+def dump_positions(total, count=None):
+    """Byte positions of a dump of a `total`-byte output: all of them when the
+    output is no larger than `count` (DUMP_SAMPLES), else `count` positions
+    drawn by a seeded generator (sorted; the same for the same `total`)."""
+    import numpy as np
+    count = DUMP_SAMPLES if count is None else count
+    if total <= count:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=count, dtype=np.int64))
+
+
+def dump_outputs(torch, out_dir, reps, restored, n, objects, L, Ls, size, rank=0):
+    """--dump-outputs: what a caller of the timed path receives after the last
+    step, as float32 .npy files.  `replicas` is the byte array [n][objects][L]
+    (the stride padding between replicas is never written and is left out),
+    `restored` the byte array [objects][size]; each is dumped at
+    dump_positions() of its flattened length, and `*_edges` hold the first and
+    last DUMP_EDGE bytes of every replica row and of the restored batch (the
+    first tile and the trailers of the last object).  Ranks above 0 write
+    <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    dev = reps.device
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), t.to(torch.float32).cpu().numpy())
+
+    p = dump_positions(n * objects * L)
+    r, rem = np.divmod(p, objects * L)
+    o, j = np.divmod(rem, L)
+    save("replicas", reps.view(-1)[torch.from_numpy(r * (objects * Ls) + o * Ls + j).to(dev)])
+    save("restored", restored.view(-1)[torch.from_numpy(dump_positions(objects * size)).to(dev)])
+    e = min(DUMP_EDGE, L)
+    last = (objects - 1) * Ls + L
+    save("replicas_edges", torch.cat([reps[:, :e], reps[:, last - e:last]], dim=1))
+    e = min(DUMP_EDGE, objects * size)
+    save("restored_edges", torch.cat([restored[:e], restored[objects * size - e:objects * size]]))
+    return ["replicas", "restored", "replicas_edges", "restored_edges"]
 
 
 def save_temp_leg(torch, chunk, dev, stream, inp, objects, size, k, n, L, Ls, timed, gib, batches=8):
@@ -629,10 +694,11 @@ def main():
     def repair():
         chunk.restore_device(k, nodes, chunk_ptrs, L, Ls, padding, objects, restored, size)
 
+    full = args.full
     c4_pre = None
-    if not args.no_c4 and not args.no_jit:
+    if full and not args.no_c4 and not args.no_jit:
         c4_pre = c4_jit_prebuild(32, [r for r in range(40) if r % 5][:32])
-    if not args.no_jit:
+    if full and not args.no_jit:
         chunk.jit_set_mode(0)  # (the AOT timing below first)
     for _ in range(args.warmup):
         encode()
@@ -641,7 +707,7 @@ def main():
     # set until the set's own kernel is loaded (every first-seen set, every
     # deployment without the JIT helper): its repair time, beside the metric.
     aot_ms = None
-    if not args.no_jit:
+    if full and not args.no_jit:
         torch.cuda.synchronize(dev)
         a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a0.record(stream)
@@ -651,6 +717,7 @@ def main():
         torch.cuda.synchronize(dev)
         aot_ms = a0.elapsed_time(a1) / args.steps
         aot_name = kernel_names(k, n, nodes, size, L, objects)[1]
+    if not args.no_jit:
         chunk.jit_set_mode(1)
     # The survivor set's own restore kernel (vds_amd/csrc/vds_ec_jit.cpp) is
     # compiled in the background from the set's second use; a repair pass
@@ -694,12 +761,16 @@ def main():
     enc_ms = sum(a.elapsed_time(b) for a, b, _ in ev) / args.steps
     rep_ms = sum(b.elapsed_time(c) for _, b, c in ev) / args.steps
 
+    dumped = None
+    if args.dump_outputs:  # the last timed step's replicas and restored objects, before any other leg runs
+        dumped = dump_outputs(torch, args.dump_outputs, reps, restored, n, objects, L, Ls, size, rank)
+
     # Fused repair, reported beside the metric, not in
     # it: regenerate the m erased replicas of every object straight from the
     # k survivors (the reference's repair restores and re-encodes instead).
     regen_out = reps[erased[0]] if erased and erased[0] < n else None
     regen_ms = None
-    if regen_out is not None and len(erased) == m:
+    if full and regen_out is not None and len(erased) == m:
         # written over the erased replicas' own buffers: same bytes, same place
         def regenerate():
             chunk.regenerate_device(k, nodes, chunk_ptrs, L, Ls, objects, erased,
@@ -723,17 +794,19 @@ def main():
 
     # Replica names, also beside the metric: SHA-256 of
     # every replica of the batch, one lane per replica (reps is [n][objects][L]).
-    digests = torch.empty((n * objects, 32), dtype=torch.uint8, device=dev)
-    chunk.sha256_device(reps, L, Ls, n * objects, digests)
-    torch.cuda.synchronize(dev)
-    h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    h0.record(stream)
-    chunk.sha256_device(reps, L, Ls, n * objects, digests)
-    h1.record(stream)
-    torch.cuda.synchronize(dev)
-    sha_ms = h0.elapsed_time(h1)
-    if world > 1:
-        sha_ms = max_over_ranks([sha_ms], dist, dev)[0]
+    digests = sha_ms = None
+    if full:
+        digests = torch.empty((n * objects, 32), dtype=torch.uint8, device=dev)
+        chunk.sha256_device(reps, L, Ls, n * objects, digests)
+        torch.cuda.synchronize(dev)
+        h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        h0.record(stream)
+        chunk.sha256_device(reps, L, Ls, n * objects, digests)
+        h1.record(stream)
+        torch.cuda.synchronize(dev)
+        sha_ms = h0.elapsed_time(h1)
+        if world > 1:
+            sha_ms = max_over_ranks([sha_ms], dist, dev)[0]
 
     ms_per_step = elapsed / args.steps * 1e3
     total_bytes = world * objects * size
@@ -753,7 +826,7 @@ def main():
     # reference's malloc'd replica buffers guarantee 16-byte alignment only),
     # beside the metric: min(256, objects) of the same objects.
     align16 = None
-    if args.replica_align != 16 and not args.no_align16:
+    if full and args.replica_align != 16 and not args.no_align16:
         del reps, digests, regen_out
         torch.cuda.empty_cache()
         o16 = min(256, objects)
@@ -798,10 +871,10 @@ def main():
     del inp, restored
     torch.cuda.empty_cache()
     c4 = None
-    if not args.no_c4:
+    if full and not args.no_c4:
         c4 = c4_leg(torch, chunk, dev, stream, args, rank, world, dist if world > 1 else None, c4_pre)
     live = None
-    if not args.no_live:
+    if full and not args.no_live:
         live = live_shape(torch, chunk, dev, torch.cuda.Stream(dev), args.live_objects, args.steps, args.warmup,
                           align=args.replica_align)
 
@@ -812,6 +885,8 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
+        "dumped_outputs": dumped,
         "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -828,7 +903,7 @@ def main():
         "repair_ms": round(rep_ms, 3),
         "regenerate_GiBps": round(world * objects * size / (regen_ms * 1e-3) / 2**30, 3) if regen_ms else None,
         "regenerate_ms": round(regen_ms, 3) if regen_ms else None,
-        "sha256_replicas_GiBps": round(world * objects * n * L / (sha_ms * 1e-3) / 2**30, 3),
+        "sha256_replicas_GiBps": round(world * objects * n * L / (sha_ms * 1e-3) / 2**30, 3) if sha_ms else None,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
                      "traffic_source": traffic_src, "algorithmic_bytes_per_launch": dom_bytes,
@@ -844,7 +919,7 @@ def main():
         "live_shape": live,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(k, n, size, nodes, args.cpu_objects)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -2,7 +2,9 @@
 
 1. The reference's own kernel/vds_data/gf.h, compiled unmodified into
    oracle/_ref/gf_ref (oracle/Makefile), against the oracle's GF arithmetic:
-   every 8-bit pair and a structured + random set of 16-bit pairs.
+   every 8-bit pair and a structured + random set of 16-bit pairs.  Where
+   gf_ref is not built, the digests recorded from its dumps
+   (tests/golden/ref_gf_digests.json) stand in for it.
 2. The known-answer vectors recorded from the reference in SURVEY.md 8(a)/(c)
    (tests/golden/survey_kats.json) and the GF(2^3) table of
    tests/test_vds_data/gf_tests.cpp:9-38.
@@ -10,6 +12,7 @@
 4. The reference's round-trip tests re-hosted on the oracle
    (chunk_tests.cpp:10-162), seeded.
 """
+import hashlib
 import json
 import os
 import subprocess
@@ -71,23 +74,64 @@ def test_survey_kats():
 REF_GF = O.REF_GF
 
 
-@pytest.mark.skipif(not os.path.exists(REF_GF), reason="oracle/_ref/gf_ref not built (reference tree absent)")
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _ref_gf_pairs(mode):
+    """The operand pairs oracle/ref_gf_harness.cpp feeds the reference's gf.h,
+    in its order."""
+    if mode == "gf3":
+        i, j = np.divmod(np.arange(64), 8)
+        return i.astype(np.uint8), j.astype(np.uint8)
+    if mode == "gf8":
+        i, j = np.divmod(np.arange(65536), 256)
+        return i.astype(np.uint8), j.astype(np.uint8)
+    fixed = np.array([0, 1, 2, 3, 5, 19, 39, 63, 0x100B, 0x8000, 0x1234, 0xFFFF], dtype=np.uint16)
+    x = np.repeat(np.arange(65536, dtype=np.uint16), fixed.size)
+    y = np.tile(fixed, 65536)
+    a = np.stack([x, y], axis=1).reshape(-1)  # (x, y), (y, x), ...
+    b = np.stack([y, x], axis=1).reshape(-1)
+    with np.errstate(over="ignore"):  # splitmix64 from 0x7664730000000000, arithmetic mod 2^64
+        z = np.uint64(0x7664730000000000) + np.arange(1, (1 << 20) + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (np.concatenate([a, z.astype(np.uint16)]),
+            np.concatenate([b, (z >> np.uint64(16)).astype(np.uint16)]))
+
+
 @pytest.mark.parametrize("mode", ["gf3", "gf8", "gf16"])
 def test_oracle_matches_compiled_reference_gf(mode, tmp_path):
-    out = tmp_path / f"{mode}.bin"
-    subprocess.run([REF_GF, mode, str(out)], check=True)
+    """Against gf_ref's dump where oracle/_ref/gf_ref is built, and always
+    against the digests recorded from it (tests/golden/ref_gf_digests.json,
+    tests/golden/make_ref_gf_digests.py): the same pairs, the same products."""
+    with open(os.path.join(GOLDEN, "ref_gf_digests.json")) as f:
+        want = json.load(f)[mode]
+    dt = np.uint16 if mode == "gf16" else np.uint8
+    names = ["a", "b", "mul"] if mode == "gf3" else ["a", "b", "mul", "div", "bits"]
+    a, b = _ref_gf_pairs(mode)
+    assert a.size == b.size == want["count"] and _sha(a) == want["a"] and _sha(b) == want["b"]
+    if os.path.exists(REF_GF):
+        out = tmp_path / f"{mode}.bin"
+        subprocess.run([REF_GF, mode, str(out)], check=True)
+        ref = dict(zip(names, _read_dump(out, dt, len(names))))
+        assert all(_sha(ref[nm]) == want[nm] for nm in names)  # the fixture is this binary's output
+        assert np.array_equal(ref["a"], a) and np.array_equal(ref["b"], b)
+    else:
+        ref = None
     if mode == "gf3":
-        a, b, p = _read_dump(out, np.uint8, 3)
         ours = np.array([O.gf_mul_bitserial(3, 0x0B, x, y) for x, y in zip(a, b)], dtype=np.uint8)
-        assert np.array_equal(ours, p)
+        assert _sha(ours) == want["mul"] and (ref is None or np.array_equal(ours, ref["mul"]))
         return
-    dt = np.uint8 if mode == "gf8" else np.uint16
-    a, b, mul, div, bits = _read_dump(out, dt, 5)
-    assert a.size == b.size == mul.size == div.size == bits.size > 0
-    assert np.array_equal(O.bulk(f"{mode}_mul", a, b), mul)
-    assert np.array_equal(O.bulk(f"{mode}_div", a, b), div)
+    mul, div = O.bulk(f"{mode}_mul", a, b), O.bulk(f"{mode}_div", a, b)
+    assert mul.dtype == dt and div.dtype == dt and mul.size == div.size == a.size > 0
+    assert _sha(mul) == want["mul"] and _sha(div) == want["div"]
+    if ref is not None:
+        assert np.array_equal(mul, ref["mul"]) and np.array_equal(div, ref["div"])
     # table multiply == bit-serial gf<m> multiply (x primitive) on every pair
-    assert np.array_equal(mul, bits)
+    assert want["mul"] == want["bits"] and (ref is None or np.array_equal(ref["mul"], ref["bits"]))
+    bits = mul  # (the reference's bit-serial products, by the digests above)
     if mode == "gf8":
         sample = slice(None)
     else:

@@ -2,7 +2,8 @@
 
 bench.py measures each roofline kernel with HIP events around its launches
 (`avg_launch_ms` in the `roofline` blocks: the headline's repair and encode,
-the AOT restore, C4's encode / survivor-set repair / AOT repair).  The same
+the AOT restore, C4's encode / survivor-set repair / AOT repair; the legs
+beyond the headline's are in a `bench.py --full` line only).  The same
 command under `rocprofv3 --kernel-trace --stats` lists every kernel symbol's
 average duration; the run-time compiled kernels carry their survivor set in
 the symbol (vds_ec_jit.cpp kernel_name), so each has a line of its own.

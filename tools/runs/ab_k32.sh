@@ -9,6 +9,7 @@
 # A variant "env:NAME=VALUE" runs the default library with that variable set
 # (label NAME_VALUE).
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-scratch/runs}; mkdir -p $OUT  # logs go under $OUT
 OBJ=${AB_OBJECTS:-256}
 ROUNDS=${AB_ROUNDS:-3}
 K=${AB_K:-32}
@@ -16,13 +17,13 @@ M=${AB_M:-8}
 summ() { tail -1 "$1" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$2', 'enc_ms',d['encode_ms'],'rep_ms',d['repair_ms'],'aot_ms',d.get('restore_aot_ms'),'value',d['value'])"; }
 one() {  # one() LIB NAME TAG
   if [ "${1#env:}" != "$1" ]; then
-    env "${1#env:}" timeout -k 10 300 python bench.py --k $K --m $M --objects $OBJ --steps 10 --warmup 3 --no-cpu-baseline --no-live --no-c4 --no-align16 > gpurun_out/abk_$2_$3.log 2>&1 || exit $?
+    env "${1#env:}" timeout -k 10 300 python bench.py --full --k $K --m $M --objects $OBJ --steps 10 --warmup 3 --no-cpu-baseline --no-live --no-c4 --no-align16 > $OUT/abk_$2_$3.log 2>&1 || exit $?
   elif [ "$1" = default ]; then
-    timeout -k 10 300 python bench.py --k $K --m $M --objects $OBJ --steps 10 --warmup 3 --no-cpu-baseline --no-live --no-c4 --no-align16 > gpurun_out/abk_$2_$3.log 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --k $K --m $M --objects $OBJ --steps 10 --warmup 3 --no-cpu-baseline --no-live --no-c4 --no-align16 > $OUT/abk_$2_$3.log 2>&1 || exit $?
   else
-    VDS_EC_LIB=$1 timeout -k 10 300 python bench.py --k $K --m $M --objects $OBJ --steps 10 --warmup 3 --no-cpu-baseline --no-live --no-c4 --no-align16 > gpurun_out/abk_$2_$3.log 2>&1 || exit $?
+    VDS_EC_LIB=$1 timeout -k 10 300 python bench.py --full --k $K --m $M --objects $OBJ --steps 10 --warmup 3 --no-cpu-baseline --no-live --no-c4 --no-align16 > $OUT/abk_$2_$3.log 2>&1 || exit $?
   fi
-  summ gpurun_out/abk_$2_$3.log $2
+  summ $OUT/abk_$2_$3.log $2
 }
 label() {
   if [ "${1#env:}" != "$1" ]; then x=${1#env:}; echo "${x%%=*}_${x#*=}"

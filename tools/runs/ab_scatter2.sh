@@ -12,6 +12,6 @@ for i in 1 2; do
   VDS_EC_JIT_SCATTER=0 $T --k 32 --objects 256 --tag row32 && VDS_EC_JIT_SPB=1 $T --k 32 --objects 256 --tag scat1_32 &&
   VDS_EC_JIT_SPB=2 $T --k 32 --objects 256 --tag scat2_32 || exit 1
 done
-B="timeout -k 10 300 python bench.py --objects 256 --no-live --no-cpu-baseline --no-align16"
+B="timeout -k 10 300 python bench.py --full --objects 256 --no-live --no-cpu-baseline --no-align16"
 VDS_EC_JIT=0 $B > gpurun_out/scat2/b_syn.log 2>&1 && $B > gpurun_out/scat2/b_jit.log 2>&1 || exit 1
 for v in syn jit; do python -c "import json;d=json.loads(open('gpurun_out/scat2/b_$v.log').read().splitlines()[-1]);print('regen $v', d['regenerate_GiBps'], d['regenerate_ms'], d['repair_ms'], d['restore_kernel'])"; done

@@ -4,7 +4,7 @@ for r in 1 2 3; do
   for v in zero nozero; do
     if [ $v = zero ]; then L=""; else L=ab/nozero.so; fi
     echo "[$r] $v"
-    VDS_EC_LIB=$L timeout -k 10 300 python bench.py --objects 512 --no-live --no-align16 --no-cpu-baseline --no-c4 --steps 10 --warmup 3 > $D/b_$v$r.json 2>$D/b_$v$r.err || exit 1
+    VDS_EC_LIB=$L timeout -k 10 300 python bench.py --full --objects 512 --no-live --no-align16 --no-cpu-baseline --no-c4 --steps 10 --warmup 3 > $D/b_$v$r.json 2>$D/b_$v$r.err || exit 1
   done
 done
 python3 - <<'PY'
