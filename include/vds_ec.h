@@ -100,6 +100,39 @@ int vds_ec_encode8_device(uint8_t k, const uint8_t *replicas, uint32_t n, const 
                           uint64_t size, uint64_t in_stride, uint32_t count, uint8_t *const *outs,
                           uint64_t out_stride, unsigned flags, void *stream);
 
+/* Encode a batch of objects of DIFFERENT sizes -- the shape of the upload
+ * loop: the web client deflates and encrypts each 64 KiB piece before
+ * `upload`, so the bodies save_temp encodes (dht_network_client.cpp:62-107)
+ * almost never have the same length.  Object o is sizes[o] bytes at ins[o];
+ * replica replicas[i] of object o is written to outs[o*n + i] and occupies
+ * vds_ec_replica_size(2, k, sizes[o], flags) bytes (ins, sizes, outs: HOST
+ * arrays of `count` device pointers, `count` sizes and count*n device
+ * pointers).  Bytes equal vds_ec_encode16_device called once per object,
+ * zero-length objects (trailer only) and VDS_EC_F_NO_TRAILER included.
+ * Every object with a non-zero size, a 4-byte aligned input and 2-byte
+ * aligned replica pointers shares ONE bit-sliced launch when (k, n) is
+ * (16,20), (32,40) or (32,64) and replicas is 0..n-1 -- whole groups, ragged
+ * tails, partial last stripes and trailers alike; every other object takes
+ * vds_ec_encode16_device's route, one call each, on the same stream.  Byte
+ * API only: VDS_EC_F_CELLS is VDS_EC_EINVAL.  Every object is validated
+ * before anything is enqueued, and before the device is looked for (null
+ * pointers where a length is non-zero, k == 0, count >= 2^30,
+ * VDS_EC_F_NO_TRAILER with a size that is not a multiple of 2k:
+ * VDS_EC_EINVAL).  Nothing synchronises; the launch's tables ride the pinned
+ * parameter ring.  Only bytes [ins[o], ins[o] + sizes[o]) are read and only
+ * the replicas' own bytes are written.                                       */
+int vds_ec_encode16_batch_device(uint16_t k, const uint16_t *replicas, uint32_t n, uint32_t count,
+                                 const uint8_t *const *ins, const uint64_t *sizes, uint8_t *const *outs,
+                                 unsigned flags, void *stream);
+/* The route vds_ec_encode16_batch_device takes for these arguments (host only,
+ * nothing is dereferenced but the host arrays; the planning is shared with
+ * the call itself): 2 when at least one object rides the shared bit-sliced
+ * launch, else 1 (invalid arguments too).  *fast_objects (may be NULL)
+ * receives the number of objects that ride it.                               */
+int vds_ec_encode16_batch_path(uint16_t k, const uint16_t *replicas, uint32_t n, uint32_t count,
+                               const uint8_t *const *ins, const uint64_t *sizes, uint8_t *const *outs,
+                               unsigned flags, uint32_t *fast_objects);
+
 /* Restore `count` objects from k replicas each: replica j (id nodes[j]) of
  * object o at chunks[j] + o*chunk_stride (chunks: HOST array of k device
  * pointers), chunk_size bytes each (trailer included).  The restored object

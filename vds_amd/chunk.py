@@ -338,6 +338,44 @@ def regenerate_batch_device(k: int, nodes: Sequence[Sequence[int]], chunks: Sequ
           "regenerate16_batch_device")
 
 
+def _encode_batch_args(k: int, replicas: Sequence[int], ins, sizes, outs):
+    """The host arrays of the batched encode: ins (count device pointers),
+    sizes (count) and outs (count x n device pointers, row o = object o's
+    replicas), from sequences or numpy arrays of ints.  The arrays are
+    returned too: they must outlive the call."""
+    ids = _ids(replicas, 2)
+    ip = np.ascontiguousarray(np.asarray(ins, dtype=np.uint64).reshape(-1))
+    sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint64).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    if sz.size != ip.size or op.size != ip.size * ids.size:
+        raise VdsEcError(_lib.EINVAL, "encode_batch: ins, sizes and outs do not describe one batch")
+    return ids, ip, sz, op
+
+
+def encode_batch_device(k: int, replicas: Sequence[int], ins, sizes, outs, write_padding: bool = True,
+                        stream=None) -> None:
+    """vds_ec_encode16_batch_device: object o (sizes[o] bytes at the device
+    pointer ins[o]) encoded into the device pointers outs[o][i], one per
+    replica id; objects of any sizes share one bit-sliced launch."""
+    ids, ip, sz, op = _encode_batch_args(k, replicas, ins, sizes, outs)
+    check(_lib.lib().vds_ec_encode16_batch_device(k, _idp(ids, 2), ids.size, ip.size, ip.ctypes.data_as(_lib.vpp),
+                                                  sz.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+                                                  0 if write_padding else F_NO_TRAILER, _stream_ptr(stream)),
+          "encode16_batch_device")
+
+
+def encode_batch_path(k: int, replicas: Sequence[int], ins, sizes, outs, write_padding: bool = True):
+    """vds_ec_encode16_batch_path: (path, fast_objects) of the batch call with
+    these arguments -- 2 when objects ride the shared bit-sliced launch, and
+    how many do.  Host only: the pointers are never dereferenced."""
+    ids, ip, sz, op = _encode_batch_args(k, replicas, ins, sizes, outs)
+    fast = C.c_uint32(0)
+    path = _lib.lib().vds_ec_encode16_batch_path(k, _idp(ids, 2), ids.size, ip.size, ip.ctypes.data_as(_lib.vpp),
+                                                 sz.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+                                                 0 if write_padding else F_NO_TRAILER, C.byref(fast))
+    return int(path), int(fast.value)
+
+
 def regenerate_host(k: int, nodes: Sequence[int], chunks: Sequence, targets: Sequence[int]) -> list:
     """vds_ec_regenerate16_host: replicas `targets` of one object from k
     survivor replicas (host buffers), bytes as restore + re-encode."""

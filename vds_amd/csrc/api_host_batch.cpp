@@ -133,6 +133,7 @@ BatchRing *batch_ring(int dev) {
 
 struct Group {
   uint32_t o0, cnt;
+  bool mixed = false;  // encode: objects of different sizes (merge_mixed_groups)
 };
 
 // Runs of consecutive objects with equal key(o), at most kGroupBytes of
@@ -148,6 +149,30 @@ std::vector<Group> make_groups(uint32_t count, Key key, Bytes bytes) {
       acc += b;
     } else {
       g.push_back({o, 1});
+      acc = b;
+    }
+  }
+  return g;
+}
+
+// Encode: consecutive one-object groups -- objects whose neighbours have other
+// sizes, the usual upload (every body deflated and encrypted to its own
+// length) -- merged into mixed groups of at most kGroupBytes, each encoded by
+// one vds_ec_encode16_batch_device call.  Runs of equal sizes, and an object
+// with no such neighbour, keep their groups (and the slab shortcuts).
+template <typename Bytes>
+std::vector<Group> merge_mixed_groups(const std::vector<Group> &in, Bytes bytes) {
+  std::vector<Group> g;
+  uint64_t acc = 0;
+  for (const Group &x : in) {
+    const uint64_t b = x.cnt == 1 ? bytes(x.o0) : 0;
+    if (x.cnt == 1 && !g.empty() && g.back().o0 + g.back().cnt == x.o0 && (g.back().mixed || g.back().cnt == 1) &&
+        acc + b <= kGroupBytes) {
+      ++g.back().cnt;
+      g.back().mixed = true;
+      acc += b;
+    } else {
+      g.push_back(x);
       acc = b;
     }
   }
@@ -292,10 +317,52 @@ int encode_host_batch(uint32_t k, const uint16_t *replicas, uint32_t n, const ui
     for (uint32_t i = 0; i < n; ++i)
       if (!outs[(uint64_t)o * n + i]) return VDS_EC_EINVAL;
   }
-  const std::vector<Group> groups = make_groups(
-      count, [&](uint32_t o) { return sizes[o]; },
-      [&](uint32_t o) { return sizes[o] + (uint64_t)n * vds_ec_replica_size(2, k, sizes[o], flags); });
+  // (the batch call is a byte API and holds the caller to the no-trailer size
+  // rule; a batch outside either keeps one group per run of equal sizes)
+  bool mix = !(flags & VDS_EC_F_CELLS);
+  if (flags & VDS_EC_F_NO_TRAILER)
+    for (uint32_t o = 0; o < count && mix; ++o) mix = sizes[o] % (2ull * k) == 0;
+  const auto obj_bytes = [&](uint32_t o) {
+    return sizes[o] + (uint64_t)n * vds_ec_replica_size(2, k, sizes[o], flags);
+  };
+  std::vector<Group> groups = make_groups(count, [&](uint32_t o) { return sizes[o]; }, obj_bytes);
+  if (mix) groups = merge_mixed_groups(groups, obj_bytes);
   return run_host_batch(groups, ndev, [&](BatchSlot &s, const Group &g) -> int {
+    if (g.mixed) {
+      // inputs back to back at 16-byte aligned offsets, replicas back to back
+      // (L is even) in the order of outs[]: one copy in, one batch call, one
+      // copy out
+      const uint64_t m = g.cnt;
+      std::vector<uint64_t> in_off(m + 1), out_off(m + 1);
+      in_off[0] = out_off[0] = 0;
+      for (uint64_t o = 0; o < m; ++o) {
+        in_off[o + 1] = (in_off[o] + sizes[g.o0 + o] + 15) & ~15ull;
+        out_off[o + 1] = out_off[o] + (uint64_t)n * vds_ec_replica_size(2, k, sizes[g.o0 + o], flags);
+      }
+      int rc = s.reserve(in_off[m], out_off[m]);
+      if (rc) return rc;
+      std::vector<Copy> in(m);
+      for (uint64_t o = 0; o < m; ++o) in[o] = {s.h_in + in_off[o], objs[g.o0 + o], sizes[g.o0 + o]};
+      parallel_copy(in);
+      if ((rc = s.reserve_dev(in_off[m], out_off[m]))) return rc;
+      hipError_t e = in_off[m] ? hipMemcpyAsync(s.d_in, s.h_in, in_off[m], hipMemcpyHostToDevice, s.stream)
+                               : hipSuccess;
+      if (e != hipSuccess) return hip_status(e);
+      std::vector<const uint8_t *> dins(m);
+      std::vector<uint8_t *> douts(m * n);
+      s.out_parts.resize(m * n);
+      for (uint64_t o = 0; o < m; ++o) {
+        const uint64_t L = vds_ec_replica_size(2, k, sizes[g.o0 + o], flags);
+        dins[o] = s.d_in + in_off[o];
+        for (uint32_t i = 0; i < n; ++i) {
+          douts[o * n + i] = s.d_out + out_off[o] + i * L;
+          s.out_parts[o * n + i] = {outs[(g.o0 + o) * n + i], s.h_out + out_off[o] + i * L, L};
+        }
+      }
+      rc = encode_batch_device(k, replicas, n, (uint32_t)m, dins.data(), sizes + g.o0, douts.data(), flags, s.stream);
+      if (rc) return rc;
+      return s.push_out(out_off[m]);
+    }
     const uint64_t size = sizes[g.o0], L = vds_ec_replica_size(2, k, size, flags), m = g.cnt;
     // caller-pinned slabs (vds_ec_host_alloc / _register): no staging copies
     bool in_slab = size > 0, out_slab = L > 0;

@@ -6,6 +6,8 @@
 //   api_param_ring.cpp  the stream-ordered parameter ring;
 //   api_batch.cpp       batched per-object-survivor restore / regenerate
 //                       planning (routes, erased-set plans, tiles);
+//   api_encode_batch.cpp  batched encode of objects of different sizes
+//                       (planning, tables, the one shared launch);
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -129,6 +131,10 @@ bool syn_solve(uint32_t k, uint32_t n, SynRestoreArgs &sa);
 int encode_device(unsigned cb, uint32_t k, const uint16_t *replicas, uint32_t n, const uint8_t *in,
                   uint64_t size, uint64_t in_stride, uint32_t count, uint8_t *const *outs,
                   uint64_t out_stride, unsigned flags, hipStream_t s);
+int encode_batch_device(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                        const uint64_t *sizes, uint8_t *const *outs, unsigned flags, hipStream_t s);
+int encode_batch_path(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                      const uint64_t *sizes, uint8_t *const *outs, unsigned flags, uint32_t *fast_objects);
 hipError_t param_acquire_n(int cnt, const size_t *bytes, ParamSlot **out);
 hipError_t param_commit(ParamSlot *sl, size_t bytes, hipStream_t s);
 hipError_t param_release(ParamSlot *sl, hipStream_t s);

@@ -21,4 +21,20 @@ hipError_t launch_encode_fast(uint32_t k, uint32_t n, const FastEncodeArgs &a, h
   return hipErrorNotSupported;
 }
 
+// The batch mode's kernels (ec_encode_batch.hpp), one translation unit each.
+hipError_t launch_encode_batch_16_20(const EncBatchLaunch &b, hipStream_t s);
+hipError_t launch_encode_batch_32_40(const EncBatchLaunch &b, hipStream_t s);
+hipError_t launch_encode_batch_32_64(const EncBatchLaunch &b, hipStream_t s);
+
+bool has_encode_batch(uint32_t k, uint32_t n) {
+  return (k == 16 && n == 20) || (k == 32 && n == 40) || (k == 32 && n == 64);
+}
+
+hipError_t launch_encode_batch(uint32_t k, uint32_t n, const EncBatchLaunch &b, hipStream_t s) {
+  if (k == 16 && n == 20) return launch_encode_batch_16_20(b, s);
+  if (k == 32 && n == 40) return launch_encode_batch_32_40(b, s);
+  if (k == 32 && n == 64) return launch_encode_batch_32_64(b, s);
+  return hipErrorNotSupported;
+}
+
 }  // namespace vds_ec

@@ -17,6 +17,9 @@
 #include "ec_device.hpp"
 
 namespace vds_ec {
+#ifdef VDS_ENC_BATCH  // included by ec_encode_batch.hpp: the batch kernels' own copy of these entities
+inline namespace enc_batch {
+#endif
 
 #ifndef VDS_ENC_PLAN_LS
 #define VDS_ENC_PLAN_LS 1  // local search after the LPT pair plan (plan_pairs)
@@ -346,10 +349,14 @@ __device__ __forceinline__ void store_replica_groups(const Plane16 &acc, uint8_t
 template <int MAP, bool STREAM, bool ROT>
 __device__ __forceinline__ void store_rep(const Plane16 &acc, uint8_t *rep, const FastEncodeArgs &a, TilePos tp,
                                           int lane, const BitMasks &bm) {
+#ifdef VDS_ENC_BATCH  // the replica id in `rep`, the tile's groups as the batch tables place them
+  store_replica_batch<ROT>(acc, rep, lane, bm);
+#else
   if constexpr (MAP == 0)  // k = 4: whole tiles of one object
     store_replica<ROT>(acc, rep + (uint64_t)tp.o * a.out_stride + 256u * tp.q + 2 * lane, bm);
   else
     store_replica_groups<STREAM, ROT>(acc, rep, a, tp, lane, bm);
+#endif
 }
 
 // Wave priority while a pass issues its stores (same-box A/B, 512 objects:
@@ -947,4 +954,7 @@ static hipError_t launch_encode_bs(const FastEncodeArgs &a, hipStream_t s) {
   return launch_encode_bs_sp<K, N, RPW, WV, false, false>(a, s);
 }
 
+#ifdef VDS_ENC_BATCH
+}  // namespace enc_batch
+#endif
 }  // namespace vds_ec

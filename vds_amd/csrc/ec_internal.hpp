@@ -74,6 +74,36 @@ struct FastEncodeArgs {
   uint8_t *outs[kMaxLaunchReplicas];  // outs[r] for replica id r = 0..N-1
 };
 
+// Batched bit-sliced encode of objects of different sizes (k_encode_batch,
+// ec_encode_batch.hpp): one launch over every 128-stripe group of every
+// object.  Device tables, built on the host: objs[e] per object, tiles[t] per
+// 2048-stripe tile.  Group j of tile t is group q[j] (stripes 128 q[j] ..) of
+// object obj[j]; an object's groups are consecutive, its last one may hold
+// fewer than 128 stripes and end in a partial stripe.  The unused groups of
+// the batch's last tile name the batch's empty object (size 0: nothing is
+// loaded or stored for it).
+constexpr uint64_t kEncBatchPtrTable = ~0ull;  // EncBatchObj::pitch: `out` is a table of pointers
+struct EncBatchObj {
+  const uint8_t *in;  // 4-byte aligned
+  uint64_t size;      // bytes; T = ceil(size / 2k) cells per replica, then the trailer
+  // replica r at out + r * pitch (replica pointers equally spaced, the usual
+  // case: 32 bytes an object whatever n), or, with pitch ==
+  // kEncBatchPtrTable, at ((uint8_t *const *)out)[r] (a device table of n
+  // pointers; any 2-byte aligned addresses)
+  uint64_t out;
+  uint64_t pitch;
+};
+struct EncBatchTile {
+  uint32_t obj[16];
+  uint32_t q[16];
+};
+struct EncBatchLaunch {
+  const EncBatchObj *objs;
+  const EncBatchTile *tiles;
+  uint32_t total_tiles;
+  uint32_t trailer;  // 1: each object's BE16 trailer (size mod 2k) is written after its cell T-1
+};
+
 // Bit-sliced runtime-coefficient restore over 512-stripe groups: the first
 // groups_per_obj groups of every object as one stream of 4-group tiles.
 struct FastRestoreArgs {
@@ -303,6 +333,10 @@ hipError_t launch_restore_generic(const GenericRestoreArgs &a, hipStream_t s);
 // Returns hipErrorNotSupported when no bit-sliced instantiation exists for (k, n).
 hipError_t launch_encode_fast(uint32_t k, uint32_t n, const FastEncodeArgs &a, hipStream_t s);
 bool has_encode_fast(uint32_t k, uint32_t n);
+// The batch kernel's shapes: (16,20), (32,40), (32,64).  The launch returns
+// hipErrorNotSupported for any other (a missing kernel is an error).
+bool has_encode_batch(uint32_t k, uint32_t n);
+hipError_t launch_encode_batch(uint32_t k, uint32_t n, const EncBatchLaunch &b, hipStream_t s);
 // SHA-256 of one message on the calling CPU thread (sha256_host.cpp)
 void sha256_host(const uint8_t *data, uint64_t len, uint8_t out[32]);
 hipError_t launch_restore_fast(uint32_t k, const FastRestoreArgs &a, hipStream_t s, bool regen = false);
