@@ -184,7 +184,9 @@ int vds_ec_regenerate16_device(uint16_t k, const uint16_t *nodes, const uint8_t 
  * launch each.  Every object is validated before anything is enqueued
  * (pointers, lengths, distinct ids: VDS_EC_ESINGULAR otherwise); nothing
  * synchronises.  count < 2^30 (VDS_EC_EINVAL otherwise).  Regenerate bytes as
- * vds_ec_regenerate16_device.                                                 */
+ * vds_ec_regenerate16_device.  Regenerated replicas are named (save_data,
+ * sync_process.cpp:313-335) with vds_ec_sha256_batch_device, passing `outs`
+ * and chunk_sizes[o] repeated ntargets times.                                 */
 int vds_ec_restore16_batch_device(uint16_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
                                   const uint64_t *chunk_sizes, const uint16_t *paddings, uint8_t *const *outs,
                                   unsigned flags, void *stream);
@@ -282,6 +284,21 @@ int vds_ec_restore16_host_split(uint16_t k, const uint16_t *nodes, const uint8_t
  * digests + 32*j (device memory).                                             */
 int vds_ec_sha256_device(const uint8_t *base, uint64_t len, uint64_t stride, uint32_t count, uint8_t *digests,
                          void *stream);
+/* SHA-256 of messages of DIFFERENT lengths in ONE launch -- the names of a
+ * ragged upload batch, whose replicas differ in length from object to object:
+ * message j is lens[j] bytes at msgs[j] (msgs, lens: HOST arrays of `count`
+ * device pointers and lengths; any alignment; lens[j] == 0 allows msgs[j] ==
+ * NULL), digest j goes to digests + 32*j (device).  One lane per message;
+ * the launch's tables ride the pinned parameter ring, the lanes are ordered by
+ * length on the host (a wave runs as long as its longest message) and every
+ * digest still lands at the caller's index.  Every argument is validated
+ * before anything is enqueued and before the device is looked for (null
+ * arrays, a null message with a non-zero length, count >= 2^30:
+ * VDS_EC_EINVAL); count == 0 is VDS_EC_OK.  Nothing synchronises.  Only the
+ * aligned 4-byte words holding at least one message byte are read (none for
+ * an empty message) and only the digests' own bytes are written.             */
+int vds_ec_sha256_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
+                               uint8_t *digests, void *stream);
 /* SHA-256 of ONE host message on the calling thread (no GPU): upload_data's
  * body hash (server_api.cpp:16) is a single chain of dependent compressions,
  * ~3 us a block in one GPU lane, so vds_ec_save_temp16_host computes it here
@@ -331,6 +348,38 @@ int vds_ec_upload_response_json(int id, const uint8_t *replica_digests, uint32_t
  * computed on the calling thread meanwhile (vds_ec_sha256_host).            */
 int vds_ec_save_temp16_host(uint16_t k, uint32_t n, const uint8_t *data, uint64_t size, uint8_t *const *outs,
                             uint8_t *replica_digests, uint8_t *data_digest, uint32_t *replica_size);
+
+/* save_temp / save_data for a BATCH of bodies of different sizes (the upload
+ * loop: dht_network_client.cpp:62-107, :582-658): vds_ec_encode16_batch_device
+ * with replicas 0..n-1 and trailers -- the same planning, the same bytes, the
+ * objects that route to vds_ec_encode16_device included --, then replica i of
+ * object o named at replica_digests + 32*(o*n + i) (device, count*n*32 bytes)
+ * and, when data_digests != NULL, the body's SHA-256 (upload_data,
+ * server_api.cpp:16) at data_digests + 32*o (device).  ins, sizes, outs: HOST
+ * arrays as vds_ec_encode16_batch_device takes them.  Every hash of the call,
+ * whatever route an object's encode took, rides ONE vds_ec_sha256_batch_device
+ * style launch after the encode; the body chains, the longest, come first in
+ * its block order.  Every argument is validated before anything is enqueued
+ * and before the device is looked for (null arrays with count > 0, null
+ * replica_digests with count*n > 0, a null pointer where a length is
+ * non-zero, k == 0, n > 65536, count >= 2^30, count*(n + 64) >= 2^32:
+ * VDS_EC_EINVAL); count == 0 is VDS_EC_OK.  Nothing synchronises.  Only the
+ * replicas' and the digests' own bytes are written.                          */
+int vds_ec_save_temp16_batch_device(uint16_t k, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                                    const uint64_t *sizes, uint8_t *const *outs, uint8_t *replica_digests,
+                                    uint8_t *data_digests, void *stream);
+/* The same from and to host memory on the calling thread's current device:
+ * bodies objs[o] (sizes[o] bytes), replicas to outs[o*n + i]
+ * (vds_ec_replica_size(2, k, sizes[o], 0) bytes each), names to
+ * replica_digests (count*n*32 host bytes), body hashes to data_digests
+ * (count*32 host bytes; may be NULL), replica_sizes[o] (may be NULL) =
+ * vds_ec_replica_size(2, k, sizes[o], 0).  Works through groups of at most
+ * 64 MiB of bodies: gathered into pinned staging, one copy to the device, the
+ * batch call above, one copy back of replicas and digests, scattered to the
+ * caller's buffers.  One device; validation as above.                       */
+int vds_ec_save_temp16_host_batch(uint16_t k, uint32_t n, uint32_t count, const uint8_t *const *objs,
+                                  const uint64_t *sizes, uint8_t *const *outs, uint8_t *replica_digests,
+                                  uint8_t *data_digests, uint32_t *replica_sizes);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

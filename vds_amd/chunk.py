@@ -32,7 +32,7 @@ __all__ = [
     "regenerate_host",
     "regenerate_device", "sha256_device", "encode_hash_host", "replica_storage_paths",
     "VdsEcError", "multipliers", "inverse", "encode_range_device", "restore_range_device", "encode_host_split",
-    "restore_host_split",
+    "restore_host_split", "sha256_batch_device", "save_temp_batch_device", "save_temp_batch",
 ]
 
 
@@ -409,6 +409,61 @@ def sha256_device(base, length: int, stride: int, count: int, digests, stream=No
     bp = base.data_ptr() if hasattr(base, "data_ptr") else int(base)
     dp = digests.data_ptr() if hasattr(digests, "data_ptr") else int(digests)
     check(_lib.lib().vds_ec_sha256_device(bp, length, stride, count, dp, _stream_ptr(stream)), "sha256_device")
+
+
+def _dev_ptr(x) -> int | None:
+    """A device address for a void* argument: a tensor, an int, or None (NULL)."""
+    if x is None:
+        return None
+    return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+
+def sha256_batch_device(msgs, lens, digests, stream=None) -> None:
+    """vds_ec_sha256_batch_device: SHA-256 of len(lens) device messages of
+    different lengths in one launch -- message j is lens[j] bytes at the
+    device pointer msgs[j] (0 allowed where lens[j] == 0); digest j goes to
+    digests + 32 j (device)."""
+    mp = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    if mp.size != ln.size:
+        raise VdsEcError(_lib.EINVAL, "sha256_batch: msgs and lens do not describe one batch")
+    check(_lib.lib().vds_ec_sha256_batch_device(ln.size, mp.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p),
+                                                _dev_ptr(digests), _stream_ptr(stream)), "sha256_batch_device")
+
+
+def save_temp_batch_device(k: int, n: int, ins, sizes, outs, replica_digests, data_digests=None,
+                           stream=None) -> None:
+    """vds_ec_save_temp16_batch_device: the batched encode of replicas 0..n-1
+    (arguments as encode_batch_device), then every replica's SHA-256 name at
+    replica_digests + 32 (o n + i) and, unless data_digests is None, every
+    body's SHA-256 at data_digests + 32 o (device buffers), all hashes in one
+    launch."""
+    _, ip, sz, op = _encode_batch_args(k, range(n), ins, sizes, outs)
+    check(_lib.lib().vds_ec_save_temp16_batch_device(k, n, ip.size, ip.ctypes.data_as(_lib.vpp),
+                                                     sz.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+                                                     _dev_ptr(replica_digests), _dev_ptr(data_digests),
+                                                     _stream_ptr(stream)), "save_temp16_batch_device")
+
+
+def save_temp_batch(k: int, n: int, bodies: Sequence) -> list:
+    """vds_ec_save_temp16_host_batch: save_temp for a batch of host bodies of
+    any sizes; per body the tuple save_temp returns (replicas, their SHA-256
+    names, the body's SHA-256, the replica size)."""
+    bufs = [_u8(b) for b in bodies]
+    count = len(bufs)
+    sz = np.asarray([b.size for b in bufs], dtype=np.uint64)
+    Ls = [replica_size(k, b.size) for b in bufs]
+    outs = [[np.empty(max(L, 1), dtype=np.uint8) for _ in range(n)] for L in Ls]
+    rd = np.empty((max(1, count * n), 32), dtype=np.uint8)
+    dd = np.empty((max(1, count), 32), dtype=np.uint8)
+    rs = np.zeros(max(1, count), dtype=np.uint32)
+    ip = (C.c_void_p * max(1, count))(*[b.ctypes.data if b.size else None for b in bufs])
+    op = (C.c_void_p * max(1, count * n))(*[o.ctypes.data for os_ in outs for o in os_])
+    check(_lib.lib().vds_ec_save_temp16_host_batch(k, n, count, ip, sz.ctypes.data_as(_lib.u64p), op, rd.ctypes.data,
+                                                   dd.ctypes.data, rs.ctypes.data_as(C.POINTER(C.c_uint32))),
+          "save_temp16_host_batch")
+    return [([r[:Ls[o]] for r in outs[o]], [bytes(x) for x in rd[o * n:(o + 1) * n]], bytes(dd[o]), int(rs[o]))
+            for o in range(count)]
 
 
 def encode_hash_host(k: int, replicas: Sequence[int], data, write_padding: bool = True):

@@ -7,19 +7,6 @@
 namespace vds_ec {
 namespace api {
 
-namespace {
-
-// What one pass over the objects leaves: the eligible objects' descriptors
-// (table addresses still as offsets into `ptrs`), the others' indices, and
-// the eligible objects' groups summed.  Kept per thread, so a caller's loop
-// allocates nothing after its first call.
-struct EncBatchScratch {
-  std::vector<EncBatchObj> objs;
-  std::vector<uint8_t *> ptrs;  // replica pointer tables of the objects whose replicas are not equally spaced
-  std::vector<uint32_t> rest;   // the objects that take encode_device, one call each
-  uint64_t groups = 0;
-};
-
 EncBatchScratch &enc_batch_scratch() {
   thread_local EncBatchScratch sc;
   return sc;
@@ -88,6 +75,8 @@ int plan_encode_batch(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t
   return VDS_EC_OK;
 }
 
+namespace {
+
 // The tables in one ring slot: descriptors (the batch's empty object last),
 // pointer tables, tiles.  Tiles are filled in stripe order, object after
 // object, and the kernel walks them with tile_range as the uniform kernel
@@ -138,12 +127,10 @@ int launch_planned(uint32_t k, uint32_t n, unsigned flags, const EncBatchScratch
 
 }  // namespace
 
-int encode_batch_device(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
-                        const uint64_t *sizes, uint8_t *const *outs, unsigned flags, hipStream_t s) {
-  EncBatchScratch &sc = enc_batch_scratch();
-  int rc = plan_encode_batch(k, replicas, n, count, ins, sizes, outs, flags, sc);
-  if (rc) return rc;
-  if ((rc = device_ready())) return rc;
+int encode_batch_run(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                     const uint64_t *sizes, uint8_t *const *outs, unsigned flags, const EncBatchScratch &sc,
+                     hipStream_t s) {
+  int rc;
   if (n == 0 || count == 0) return VDS_EC_OK;
   if (!sc.objs.empty() && (rc = launch_planned(k, n, flags, sc, s))) return rc;
   for (const uint32_t o : sc.rest) {
@@ -151,6 +138,15 @@ int encode_batch_device(uint32_t k, const uint16_t *replicas, uint32_t n, uint32
     if (rc) return rc;
   }
   return VDS_EC_OK;
+}
+
+int encode_batch_device(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                        const uint64_t *sizes, uint8_t *const *outs, unsigned flags, hipStream_t s) {
+  EncBatchScratch &sc = enc_batch_scratch();
+  int rc = plan_encode_batch(k, replicas, n, count, ins, sizes, outs, flags, sc);
+  if (rc) return rc;
+  if ((rc = device_ready())) return rc;
+  return encode_batch_run(k, replicas, n, count, ins, sizes, outs, flags, sc, s);
 }
 
 int encode_batch_path(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,

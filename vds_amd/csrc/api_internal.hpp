@@ -8,6 +8,8 @@
 //                       planning (routes, erased-set plans, tiles);
 //   api_encode_batch.cpp  batched encode of objects of different sizes
 //                       (planning, tables, the one shared launch);
+//   api_save_temp_batch.cpp  SHA-256 over messages of different lengths and
+//                       the batched save_temp built on it (device and host);
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -135,6 +137,31 @@ int encode_batch_device(uint32_t k, const uint16_t *replicas, uint32_t n, uint32
                         const uint64_t *sizes, uint8_t *const *outs, unsigned flags, hipStream_t s);
 int encode_batch_path(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
                       const uint64_t *sizes, uint8_t *const *outs, unsigned flags, uint32_t *fast_objects);
+// What plan_encode_batch's one pass over the objects leaves: the eligible
+// objects' descriptors in the caller's order (table addresses still as offsets
+// into `ptrs`), the others' indices in ascending order, and the eligible
+// objects' groups summed.  Kept per thread, so a caller's loop allocates
+// nothing after its first call.
+struct EncBatchScratch {
+  std::vector<EncBatchObj> objs;
+  std::vector<uint8_t *> ptrs;  // replica pointer tables of the objects whose replicas are not equally spaced
+  std::vector<uint32_t> rest;   // the objects that take encode_device, one call each
+  uint64_t groups = 0;
+};
+EncBatchScratch &enc_batch_scratch();
+int plan_encode_batch(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                      const uint64_t *sizes, uint8_t *const *outs, unsigned flags, EncBatchScratch &sc);
+// Enqueue what the plan describes (the device is ready): the shared launch, then the rest one call each.
+int encode_batch_run(uint32_t k, const uint16_t *replicas, uint32_t n, uint32_t count, const uint8_t *const *ins,
+                     const uint64_t *sizes, uint8_t *const *outs, unsigned flags, const EncBatchScratch &sc,
+                     hipStream_t s);
+int sha256_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens, uint8_t *digests,
+                        hipStream_t s);
+int save_temp_batch_device(uint32_t k, uint32_t n, uint32_t count, const uint8_t *const *ins, const uint64_t *sizes,
+                           uint8_t *const *outs, uint8_t *replica_digests, uint8_t *data_digests, hipStream_t s);
+int save_temp_host_batch(uint32_t k, uint32_t n, uint32_t count, const uint8_t *const *objs, const uint64_t *sizes,
+                         uint8_t *const *outs, uint8_t *replica_digests, uint8_t *data_digests,
+                         uint32_t *replica_sizes);
 hipError_t param_acquire_n(int cnt, const size_t *bytes, ParamSlot **out);
 hipError_t param_commit(ParamSlot *sl, size_t bytes, hipStream_t s);
 hipError_t param_release(ParamSlot *sl, hipStream_t s);

@@ -104,6 +104,35 @@ struct EncBatchLaunch {
   uint32_t trailer;  // 1: each object's BE16 trailer (size mod 2k) is written after its cell T-1
 };
 
+// SHA-256 over messages of different lengths (k_sha256_batch, sha256.hip): one
+// lane per message, one launch.  Device tables, built on the host.  A group is
+// m messages of one length whose digests are contiguous -- the n replicas of
+// one object, or one message (m = 1).  Groups are laid out in lane order:
+// group g owns lanes spans[g].first .. + m - 1 (first ascending; lanes between
+// two groups belong to nobody and do nothing).  wave_group[w] is the last group
+// whose first lane is <= 64 w (waves + 1 entries, the last one for lane
+// 64 waves), so a lane finds its group between two consecutive entries.
+constexpr uint64_t kShaBatchPtrTable = ~0ull;  // ShaBatchGroup::pitch: `msg` is a table of pointers
+struct ShaBatchGroup {
+  // message i at msg + i * pitch (32 bytes a group whatever m), or, with
+  // pitch == kShaBatchPtrTable, at ((const uint8_t *const *)msg)[i] (a device
+  // table of m pointers); any alignment; len == 0: never dereferenced
+  uint64_t msg;
+  uint64_t pitch;
+  uint64_t len;      // bytes of each message
+  uint64_t digests;  // digest of message i at digests + 32 i
+};
+struct ShaBatchSpan {
+  uint32_t first;  // the group's first lane
+  uint32_t m;      // its messages
+};
+struct ShaBatchLaunch {
+  const ShaBatchGroup *groups;
+  const ShaBatchSpan *spans;
+  const uint32_t *wave_group;
+  uint32_t waves;
+};
+
 // Bit-sliced runtime-coefficient restore over 512-stripe groups: the first
 // groups_per_obj groups of every object as one stream of 4-group tiles.
 struct FastRestoreArgs {
@@ -344,6 +373,8 @@ bool has_restore_fast(uint32_t k);
 // SHA-256 of count messages of len bytes at base + j * stride -> digests + 32 j (sha256.hip).
 hipError_t launch_sha256(const uint8_t *base, uint64_t len, uint64_t stride, uint32_t count, uint8_t *digests,
                          hipStream_t s);
+// SHA-256 of every message of b's groups, each digest at its group's address (sha256.hip).
+hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s);
 hipError_t launch_fill_splitmix(uint8_t *dst, uint64_t size, uint64_t seed, hipStream_t s);
 // Device -> mapped pinned host copy by a kernel (dst: the device view of the
 // host buffer; both 16-byte aligned).

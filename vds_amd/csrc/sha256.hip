@@ -176,7 +176,112 @@ __global__ __launch_bounds__(64) void k_sha256(const uint8_t *base, uint64_t len
     for (int t = 0; t < 4; ++t) dg[4 * i + t] = (uint8_t)(h[i] >> (24 - 8 * t));
 }
 
+// Messages of different lengths, one lane each: lane j finds its group between
+// its wave's two wave_group entries (ShaBatchLaunch, ec_internal.hpp), then
+// walks its own message with its own length and alignment -- aligned dwords
+// and one v_perm_b32 per word as k_sha256<false>, and the next block's 17
+// dwords issued before this block's 64 rounds (the lanes of a wave sit in
+// different messages, so nothing else hides the latency).  A wave runs as long
+// as its longest chain; the host orders the lanes by length.  Only aligned
+// dwords holding at least one message byte are read; a message of length 0
+// reads nothing (its pointer may be null).
+__global__ __launch_bounds__(64) void k_sha256_batch(ShaBatchLaunch b) {
+  const uint32_t wv = blockIdx.x;
+  const uint32_t j = wv * 64u + threadIdx.x;
+  uint32_t lo = b.wave_group[wv], hi = b.wave_group[wv + 1];
+  while (lo < hi) {  // the last group whose first lane is <= j
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (b.spans[mid].first <= j)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const ShaBatchSpan sp = b.spans[lo];
+  const uint32_t idx = j - sp.first;
+  if (idx >= sp.m) return;  // a lane between two groups, or past the last one
+  const ShaBatchGroup g = b.groups[lo];
+  const uint64_t len = g.len;
+  // (the addresses come from the tables as integers: global pointers made
+  // from them keep the loads and stores global_* rather than flat_*)
+  typedef const __attribute__((address_space(1))) uint64_t *gptr_u64;
+  typedef const __attribute__((address_space(1))) uint32_t *gptr_u32;
+  typedef __attribute__((address_space(1))) uint8_t *gptr_u8;
+  uint64_t m = 0;
+  if (len) m = g.pitch == kShaBatchPtrTable ? reinterpret_cast<gptr_u64>(g.msg)[idx] : g.msg + (uint64_t)idx * g.pitch;
+  uint32_t h[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) h[i] = kSha256H0[i];
+
+  // Whole blocks: block blk needs dwords 16 blk .. 16 blk + 16 of p, all
+  // holding message bytes while 64 blk + 68 <= len + sh.
+  const uint32_t sh = (uint32_t)(m & 3u);
+  const gptr_u32 p = reinterpret_cast<gptr_u32>(m - sh);
+  const uint32_t sel = (sh + 3u) | ((sh + 2u) << 8) | ((sh + 1u) << 16) | (sh << 24);
+  const uint64_t nfast = len + sh >= 68 ? (len + sh - 68) / 64 + 1 : 0;
+  // nx = the block's 16 dwords, top = the one after them.  (Loading the 16 from
+  // the block's own first dword, not from the second with the first carried
+  // over: with a 64-byte aligned message -- replicas in aligned slots -- each
+  // lane's loads then stay inside one 64-byte segment.)
+  uint32_t nx[16], top = 0u;
+  if (nfast) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) nx[i] = p[i];
+    top = p[16];
+  }
+  for (uint64_t blk = 0; blk < nfast; ++blk) {
+    uint32_t w[16];
+#pragma unroll
+    for (int i = 0; i < 15; ++i) w[i] = __builtin_amdgcn_perm(nx[i + 1], nx[i], sel);
+    w[15] = __builtin_amdgcn_perm(top, nx[15], sel);
+    if (blk + 1 < nfast) {  // dwords 16 (blk + 1) .. + 16: inside the message, as above
+      const gptr_u32 q = p + 16 * (blk + 1);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) nx[i] = q[i];
+      top = q[16];
+    }
+    sha256_compress(h, w);
+  }
+
+  // The rest (< 132 bytes) and the padding as k_sha256 does; with len == 0 no
+  // dword holds a message byte whatever the pointer is.
+  const uint64_t rem = len - 64 * nfast;
+  const uint32_t nb = (uint32_t)((rem + 9 + 63) / 64);
+  const uint64_t bits = len * 8;
+  const uint64_t lim = len ? len + sh : 0;  // aligned byte offsets < lim hold message bytes
+  for (uint32_t blk = 0; blk < nb; ++blk) {
+    const uint64_t q0 = 16 * (nfast + blk);
+    uint32_t raw[17];
+#pragma unroll
+    for (int i = 0; i <= 16; ++i) raw[i] = 4 * (q0 + i) < lim ? p[q0 + i] : 0u;
+    uint32_t w[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int64_t c = (int64_t)rem - (int64_t)(64 * blk + 4 * i);  // message bytes left at this word
+      uint32_t v = __builtin_amdgcn_perm(raw[i + 1], raw[i], sel);
+      if (c < 4) v = c <= 0 ? 0u : v & ~(0xFFFFFFFFu >> (8 * c));
+      if (c >= 0 && c < 4) v |= 0x80u << (24 - 8 * c);
+      w[i] = v;
+    }
+    if (blk + 1 == nb) {
+      w[14] = (uint32_t)(bits >> 32);
+      w[15] = (uint32_t)bits;
+    }
+    sha256_compress(h, w);
+  }
+  const gptr_u8 dg = reinterpret_cast<gptr_u8>(g.digests + 32ull * idx);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dg[4 * i + t] = (uint8_t)(h[i] >> (24 - 8 * t));
+}
+
 }  // namespace
+
+hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s) {
+  if (b.waves == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sha256_batch, dim3(b.waves), dim3(64), 0, s, b);
+  return hipGetLastError();
+}
 
 hipError_t launch_sha256(const uint8_t *base, uint64_t len, uint64_t stride, uint32_t count, uint8_t *digests,
                          hipStream_t s) {
