@@ -184,9 +184,9 @@ int vds_ec_regenerate16_device(uint16_t k, const uint16_t *nodes, const uint8_t 
  * launch each.  Every object is validated before anything is enqueued
  * (pointers, lengths, distinct ids: VDS_EC_ESINGULAR otherwise); nothing
  * synchronises.  count < 2^30 (VDS_EC_EINVAL otherwise).  Regenerate bytes as
- * vds_ec_regenerate16_device.  Regenerated replicas are named (save_data,
- * sync_process.cpp:313-335) with vds_ec_sha256_batch_device, passing `outs`
- * and chunk_sizes[o] repeated ntargets times.                                 */
+ * vds_ec_regenerate16_device.  To regenerate, name (save_data,
+ * sync_process.cpp:313-335) and check the replicas in one call, use
+ * vds_ec_repair16_batch_device below.                                         */
 int vds_ec_restore16_batch_device(uint16_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
                                   const uint64_t *chunk_sizes, const uint16_t *paddings, uint8_t *const *outs,
                                   unsigned flags, void *stream);
@@ -380,6 +380,69 @@ int vds_ec_save_temp16_batch_device(uint16_t k, uint32_t n, uint32_t count, cons
 int vds_ec_save_temp16_host_batch(uint16_t k, uint32_t n, uint32_t count, const uint8_t *const *objs,
                                   const uint64_t *sizes, uint8_t *const *outs, uint8_t *replica_digests,
                                   uint8_t *data_digests, uint32_t *replica_sizes);
+
+/* ------------------------------------------- repair loop and the name check
+ * As vds_ec_sha256_batch_device, and message j's digest compared with
+ * expected + 32*j (device, any alignment): verdicts[j] = 0 equal / 1
+ * different (device, count bytes).  digests may be NULL (check only: no digest
+ * is written).  Validation as vds_ec_sha256_batch_device, and null expected or
+ * verdicts with count > 0: VDS_EC_EINVAL.  Nothing synchronises.  The
+ * comparison rides the hash launch (each lane compares its own state words
+ * after its last block), so a check costs no copy-back of digests and no host
+ * loop.
+ * The download loop: the request carries every replica's name
+ * (websocket_api.cpp:193), restore_async reads the replica files by name
+ * (dht_network_client.cpp:873) and decodes them WITHOUT hashing them -- the
+ * hash check of read_data (:952-960, "Data is corrupted") is not on that path.
+ * This call over the k survivors of every object (digests == NULL), enqueued
+ * beside vds_ec_restore16_batch_device, is that missing check.               */
+int vds_ec_sha256_check_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
+                                     const uint8_t *expected, uint8_t *digests, uint8_t *verdicts, void *stream);
+
+/* The repair loop (sync_process.cpp:313-335 -> restore_async -> save_data,
+ * dht_network_client.cpp:582-658) for a batch: vds_ec_regenerate16_batch_device
+ * (same arguments, same planning, same bytes, every route), then ONE hash
+ * launch naming replica targets[o*nt + i] of object o at digests +
+ * 32*(o*nt + i) (device, count*nt*32 bytes) and, when expected != NULL,
+ * comparing it with expected + 32*(o*nt + i) (device; the names the catalogue
+ * holds, chunk_replica_data_dbo.replica_hash) into verdicts[o*nt + i] (device,
+ * count*nt bytes: 0 equal, 1 different).  With expected == NULL verdicts must
+ * be NULL too and nothing is compared.
+ * What the check covers: EVERY CELL OF EVERY SURVIVOR and the FIRST survivor's
+ * trailer.  The code is MDS: changing any cell of any of the k survivors
+ * changes that stripe's cell in every other replica, so every regenerated
+ * replica's name then differs from the catalogue's and every verdict of the
+ * object is 1 -- without hashing the survivors themselves.  The reference
+ * route reads no trailer but the first survivor's (chunk.h:408), so a wrong
+ * trailer on survivor 2..k leaves every regenerated replica, and every
+ * verdict, unchanged.
+ * Every argument is validated before anything is enqueued and before the
+ * device is looked for: the checks of vds_ec_regenerate16_batch_device
+ * (VDS_EC_ESINGULAR for repeated ids included), and null digests with
+ * count*ntargets > 0, expected and verdicts not both NULL or both non-NULL,
+ * count*(ntargets + 64) >= 2^32 (the hash launch's lanes): VDS_EC_EINVAL.
+ * count == 0 or ntargets == 0 is VDS_EC_OK.  Nothing synchronises.  Only the
+ * replicas', digests' and verdicts' own bytes are written.                   */
+int vds_ec_repair16_batch_device(uint16_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                                 const uint64_t *chunk_sizes, uint32_t ntargets, const uint16_t *targets,
+                                 uint8_t *const *outs, uint8_t *digests, const uint8_t *expected,
+                                 uint8_t *verdicts, void *stream);
+/* The same from and to host memory on the calling thread's current device:
+ * survivors chunks[o*k + j] (chunk_sizes[o] host bytes), replicas to
+ * outs[o*nt + i] (chunk_sizes[o] bytes), names to digests (count*nt*32 host
+ * bytes), expected (host, may be NULL) against them into verdicts (count*nt
+ * host bytes); *mismatches (may be NULL) receives the number of non-zero
+ * verdicts, 0 when expected is NULL.  Works through groups of at most 64 MiB
+ * of survivor bytes (a larger object is a group of its own): gathered into
+ * pinned staging with the expected names, one copy to the device, the call
+ * above, one copy back of replicas, names and verdicts, scattered to the
+ * caller.  Validation as above, every object before any transfer; and, the
+ * host having the trailers, an object whose first chunk's trailer exceeds 2k
+ * fails the whole call with VDS_EC_ERESTORE as vds_ec_regenerate16_host does. */
+int vds_ec_repair16_host_batch(uint16_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                               const uint64_t *chunk_sizes, uint32_t ntargets, const uint16_t *targets,
+                               uint8_t *const *outs, uint8_t *digests, const uint8_t *expected,
+                               uint8_t *verdicts, uint32_t *mismatches);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

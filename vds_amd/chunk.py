@@ -431,6 +431,79 @@ def sha256_batch_device(msgs, lens, digests, stream=None) -> None:
                                                 _dev_ptr(digests), _stream_ptr(stream)), "sha256_batch_device")
 
 
+def sha256_check_batch_device(msgs, lens, expected, verdicts, digests=None, stream=None) -> None:
+    """vds_ec_sha256_check_batch_device: as sha256_batch_device, and digest j
+    compared with the 32 bytes at expected + 32 j into verdicts[j] (device
+    buffers; 0 equal, 1 different).  digests None: check only."""
+    mp = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    if mp.size != ln.size:
+        raise VdsEcError(_lib.EINVAL, "sha256_check_batch: msgs and lens do not describe one batch")
+    check(_lib.lib().vds_ec_sha256_check_batch_device(ln.size, mp.ctypes.data_as(_lib.vpp),
+                                                      ln.ctypes.data_as(_lib.u64p), _dev_ptr(expected),
+                                                      _dev_ptr(digests), _dev_ptr(verdicts), _stream_ptr(stream)),
+          "sha256_check_batch_device")
+
+
+def repair_batch_device(k: int, nodes: Sequence[Sequence[int]], chunks: Sequence[Sequence[int]],
+                        chunk_sizes: Sequence[int], targets: Sequence[Sequence[int]],
+                        outs: Sequence[Sequence[int]], digests, expected=None, verdicts=None, stream=None) -> None:
+    """vds_ec_repair16_batch_device: regenerate_batch_device, then replica
+    targets[o][i] named at digests + 32 (o nt + i) and, with expected, checked
+    against expected + 32 (o nt + i) into verdicts[o nt + i] (device buffers),
+    names and verdicts in one launch."""
+    count = len(nodes)
+    nt = len(targets[0]) if count else 0
+    ids = _ids([r for nd in nodes for r in nd], 2)
+    tg = _ids([t for ts in targets for t in ts], 2)
+    cp = (C.c_void_p * max(1, count * k))(*[int(c) for ch in chunks for c in ch])
+    cs = np.asarray(chunk_sizes, dtype=np.uint64)
+    op = (C.c_void_p * max(1, count * nt))(*[int(x) for os_ in outs for x in os_])
+    check(_lib.lib().vds_ec_repair16_batch_device(k, count, _idp(ids, 2), cp, cs.ctypes.data_as(_lib.u64p), nt,
+                                                  _idp(tg, 2), op, _dev_ptr(digests), _dev_ptr(expected),
+                                                  _dev_ptr(verdicts), _stream_ptr(stream)),
+          "repair16_batch_device")
+
+
+def repair_batch(k: int, horcruxes: Sequence[Mapping[int, object]], targets: Sequence[Sequence[int]],
+                 expected=None) -> list:
+    """vds_ec_repair16_host_batch: the repair loop for a batch of host objects.
+    horcruxes[o] maps replica id -> bytes (its first k entries are used, in
+    order); targets[o] lists the ids to regenerate (every object the same
+    number); expected, when given, holds per object the names those replicas
+    must have (32 bytes each).  Returns per object (replicas, names, verdicts
+    or None)."""
+    count = len(horcruxes)
+    nt = len(targets[0]) if count else 0
+    items = [list(h.items())[:k] for h in horcruxes]
+    if any(len(it) < k for it in items) or any(len(t) != nt for t in targets):
+        raise VdsEcError(_lib.EINVAL, "repair_batch")
+    ids = _ids([r for it in items for r, _ in it], 2)
+    tg = _ids([t for ts in targets for t in ts], 2)
+    bufs = [[_u8(v) for _, v in it] for it in items]
+    if any(b.size != bs[0].size for bs in bufs for b in bs):
+        raise VdsEcError(_lib.EINVAL, "repair_batch")
+    cs = np.asarray([bs[0].size for bs in bufs], dtype=np.uint64)
+    outs = [[np.empty(max(int(c), 1), dtype=np.uint8) for _ in range(nt)] for c in cs]
+    dg = np.empty((max(1, count * nt), 32), dtype=np.uint8)
+    ex = vd = None
+    if expected is not None:
+        ex = np.ascontiguousarray(np.frombuffer(b"".join(bytes(e) for es in expected for e in es), dtype=np.uint8))
+        if ex.size != 32 * count * nt:
+            raise VdsEcError(_lib.EINVAL, "repair_batch: expected does not hold one name per target")
+        vd = np.zeros(max(1, count * nt), dtype=np.uint8)
+    bad = C.c_uint32(0)
+    cp = (C.c_void_p * max(1, count * k))(*[b.ctypes.data for bs in bufs for b in bs])
+    op = (C.c_void_p * max(1, count * nt))(*[o.ctypes.data for os_ in outs for o in os_])
+    check(_lib.lib().vds_ec_repair16_host_batch(k, count, _idp(ids, 2), cp, cs.ctypes.data_as(_lib.u64p), nt,
+                                                _idp(tg, 2), op, dg.ctypes.data,
+                                                ex.ctypes.data if ex is not None and ex.size else None,
+                                                vd.ctypes.data if vd is not None and ex.size else None,
+                                                C.byref(bad)), "repair16_host_batch")
+    return [([r[:int(cs[o])] for r in outs[o]], [bytes(x) for x in dg[o * nt:(o + 1) * nt]],
+             None if vd is None else [int(v) for v in vd[o * nt:(o + 1) * nt]]) for o in range(count)]
+
+
 def save_temp_batch_device(k: int, n: int, ins, sizes, outs, replica_digests, data_digests=None,
                            stream=None) -> None:
     """vds_ec_save_temp16_batch_device: the batched encode of replicas 0..n-1

@@ -324,6 +324,16 @@ constexpr bool dual_enabled() { return VDS_BATCH_DUAL != 0; }
 // under one lock hold, solving what the store lacks -- and then writes its
 // descriptors with dense plan numbers.  (Claims through a shared counter and
 // per-set store locking from eight threads made that pass 4x slower.)
+
+// In a spin on another core's store: the hint that frees the core's
+// pipeline for its sibling thread (a no-op where there is none).
+inline void cpu_pause() {
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+  __builtin_ia32_pause();
+#elif defined(__aarch64__) && !defined(__HIP_DEVICE_COMPILE__)
+  __asm__ __volatile__("yield");
+#endif
+}
 inline uint32_t plan_class_rank(uint32_t ms) { return ms == 1 ? 0 : ms == 2 ? 1 : ms == kMsPerm ? 2 : 3; }
 struct SynBatchBuild {
   static constexpr uint32_t kPending = 0xFFFFFFFFu;
@@ -379,8 +389,10 @@ struct SynBatchBuild {
 
   // A builder is per thread and reused (batch_scratch): the vectors keep
   // their capacity, so a steady stream of calls allocates nothing.  The
-  // claim table is made ready for `count` objects.
-  void reset(uint32_t k_, uint32_t n_, uint32_t count) {
+  // claim table is made ready for `count` objects -- when the syndrome route
+  // is possible at all (`syn`): no other route claims a plan, and the table
+  // is 32 bytes an object.
+  void reset(uint32_t k_, uint32_t n_, uint32_t count, bool syn) {
     k = k_;
     n = n_;
     regen = false;
@@ -389,8 +401,8 @@ struct SynBatchBuild {
     objs = nullptr;
     nobj = 0;
     unsigned bits = 4;
-    while ((1ull << bits) < 2ull * count) ++bits;
-    if (ht.size() != (1ull << bits)) {
+    while (syn && (1ull << bits) < 2ull * count) ++bits;
+    if (syn && ht.size() != (1ull << bits)) {
       ht.assign(1ull << bits, Entry{0, kPending, 0});
       for (PartPlans &q : pp) q.hused.clear();
     }
@@ -446,6 +458,7 @@ struct SynBatchBuild {
       if (cur == hk) {
         uint32_t v;
         while ((v = __atomic_load_n(&ht[i].val, __ATOMIC_ACQUIRE)) == kPending) {
+          cpu_pause();
         }  // (the claimer stores it right after numbering it)
         return v;
       }
@@ -958,7 +971,7 @@ int restore_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, cons
   BatchIndex &ix = sc.ix;
   ix.reset(count);
   SynBatchBuild &bb = sc.bb;
-  bb.reset(k, n, count);
+  bb.reset(k, n, count, syn);
   FirstError err;
   parallel_parts(count, [&](unsigned part, uint32_t o0, uint32_t o1) {
     PartTotals tot;
@@ -1082,7 +1095,7 @@ int regenerate_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, c
   BatchIndex &ix = sc.ix;
   ix.reset(count);
   SynBatchBuild &bb = sc.bb;
-  bb.reset(k, n, count);
+  bb.reset(k, n, count, syn);
   bb.regen = true;
   FirstError err;
   parallel_parts(count, [&](unsigned part, uint32_t o0, uint32_t o1) {

@@ -10,6 +10,8 @@
 //                       (planning, tables, the one shared launch);
 //   api_save_temp_batch.cpp  SHA-256 over messages of different lengths and
 //                       the batched save_temp built on it (device and host);
+//                       its check mode and the batched repair (regenerate,
+//                       name, check);
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -162,6 +164,14 @@ int save_temp_batch_device(uint32_t k, uint32_t n, uint32_t count, const uint8_t
 int save_temp_host_batch(uint32_t k, uint32_t n, uint32_t count, const uint8_t *const *objs, const uint64_t *sizes,
                          uint8_t *const *outs, uint8_t *replica_digests, uint8_t *data_digests,
                          uint32_t *replica_sizes);
+int sha256_check_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
+                              const uint8_t *expected, uint8_t *digests, uint8_t *verdicts, hipStream_t s);
+int repair_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                        const uint64_t *chunk_sizes, uint32_t nt, const uint16_t *targets, uint8_t *const *outs,
+                        uint8_t *digests, const uint8_t *expected, uint8_t *verdicts, hipStream_t s);
+int repair_host_batch(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                      const uint64_t *chunk_sizes, uint32_t nt, const uint16_t *targets, uint8_t *const *outs,
+                      uint8_t *digests, const uint8_t *expected, uint8_t *verdicts, uint32_t *mismatches);
 hipError_t param_acquire_n(int cnt, const size_t *bytes, ParamSlot **out);
 hipError_t param_commit(ParamSlot *sl, size_t bytes, hipStream_t s);
 hipError_t param_release(ParamSlot *sl, hipStream_t s);

@@ -132,6 +132,20 @@ struct ShaBatchLaunch {
   const uint32_t *wave_group;
   uint32_t waves;
 };
+// Check mode (k_sha256_batch<true>): checks[g] beside groups[g], same order.
+// A lane compares its digest with the 32 bytes at expected + 32 i and writes
+// the verdict byte at verdicts + i: 0 equal, 1 different (any alignment, both).
+// expected == 0: the group is not checked and no verdict byte of it is
+// written.  In this mode a group whose ShaBatchGroup::digests is 0 writes no
+// digest (check only).
+struct ShaBatchCheck {
+  uint64_t expected;
+  uint64_t verdicts;
+};
+struct ShaBatchCheckLaunch {
+  ShaBatchLaunch b;
+  const ShaBatchCheck *checks;
+};
 
 // Bit-sliced runtime-coefficient restore over 512-stripe groups: the first
 // groups_per_obj groups of every object as one stream of 4-group tiles.
@@ -375,6 +389,8 @@ hipError_t launch_sha256(const uint8_t *base, uint64_t len, uint64_t stride, uin
                          hipStream_t s);
 // SHA-256 of every message of b's groups, each digest at its group's address (sha256.hip).
 hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s);
+// The same, and every group's check (ShaBatchCheck) in the same launch.
+hipError_t launch_sha256_check_batch(const ShaBatchCheckLaunch &c, hipStream_t s);
 hipError_t launch_fill_splitmix(uint8_t *dst, uint64_t size, uint64_t seed, hipStream_t s);
 // Device -> mapped pinned host copy by a kernel (dst: the device view of the
 // host buffer; both 16-byte aligned).

@@ -14,6 +14,8 @@
 // big-endian message words with one v_perm_b32 each.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "ec_internal.hpp"
 
 namespace vds_ec {
@@ -176,6 +178,10 @@ __global__ __launch_bounds__(64) void k_sha256(const uint8_t *base, uint64_t len
     for (int t = 0; t < 4; ++t) dg[4 * i + t] = (uint8_t)(h[i] >> (24 - 8 * t));
 }
 
+// (the batch kernel's tables, whichever launch struct its instance takes)
+__device__ __forceinline__ const ShaBatchLaunch &tables(const ShaBatchLaunch &l) { return l; }
+__device__ __forceinline__ const ShaBatchLaunch &tables(const ShaBatchCheckLaunch &l) { return l.b; }
+
 // Messages of different lengths, one lane each: lane j finds its group between
 // its wave's two wave_group entries (ShaBatchLaunch, ec_internal.hpp), then
 // walks its own message with its own length and alignment -- aligned dwords
@@ -185,7 +191,16 @@ __global__ __launch_bounds__(64) void k_sha256(const uint8_t *base, uint64_t len
 // as its longest chain; the host orders the lanes by length.  Only aligned
 // dwords holding at least one message byte are read; a message of length 0
 // reads nothing (its pointer may be null).
-__global__ __launch_bounds__(64) void k_sha256_batch(ShaBatchLaunch b) {
+//
+// CHECK (the repair and download loops: the catalogue holds the name every
+// replica must have): after its last compression, when only h[8] is live, the
+// lane also compares its digest with its group's expected bytes and writes a
+// verdict byte (ShaBatchCheck, ec_internal.hpp); the expected bytes are read
+// as the message is, from the aligned dwords holding at least one of them.
+template <bool CHECK>
+__global__ __launch_bounds__(64) void k_sha256_batch(
+    std::conditional_t<CHECK, ShaBatchCheckLaunch, ShaBatchLaunch> launch) {
+  const ShaBatchLaunch &b = tables(launch);
   const uint32_t wv = blockIdx.x;
   const uint32_t j = wv * 64u + threadIdx.x;
   uint32_t lo = b.wave_group[wv], hi = b.wave_group[wv + 1];
@@ -268,18 +283,44 @@ __global__ __launch_bounds__(64) void k_sha256_batch(ShaBatchLaunch b) {
     }
     sha256_compress(h, w);
   }
-  const gptr_u8 dg = reinterpret_cast<gptr_u8>(g.digests + 32ull * idx);
+  if (!CHECK || g.digests) {
+    const gptr_u8 dg = reinterpret_cast<gptr_u8>(g.digests + 32ull * idx);
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) dg[4 * i + t] = (uint8_t)(h[i] >> (24 - 8 * t));
+      for (int t = 0; t < 4; ++t) dg[4 * i + t] = (uint8_t)(h[i] >> (24 - 8 * t));
+  }
+  if constexpr (CHECK) {
+    const ShaBatchCheck c = launch.checks[lo];
+    if (c.expected == 0) return;
+    // expected byte 4i..4i+3 big-endian = word i of the digest: dwords 0..7 of
+    // ep hold expected bytes whatever esh is, dword 8 only when esh != 0
+    const uint64_t e = c.expected + 32ull * idx;
+    const uint32_t esh = (uint32_t)(e & 3u);
+    const gptr_u32 ep = reinterpret_cast<gptr_u32>(e - esh);
+    const uint32_t esel = (esh + 3u) | ((esh + 2u) << 8) | ((esh + 1u) << 16) | (esh << 24);
+    uint32_t raw[9];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) raw[i] = ep[i];
+    raw[8] = esh ? ep[8] : 0u;
+    uint32_t diff = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) diff |= h[i] ^ __builtin_amdgcn_perm(raw[i + 1], raw[i], esel);
+    reinterpret_cast<gptr_u8>(c.verdicts)[idx] = diff ? 1 : 0;
+  }
 }
 
 }  // namespace
 
 hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s) {
   if (b.waves == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_sha256_batch, dim3(b.waves), dim3(64), 0, s, b);
+  hipLaunchKernelGGL(k_sha256_batch<false>, dim3(b.waves), dim3(64), 0, s, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_sha256_check_batch(const ShaBatchCheckLaunch &c, hipStream_t s) {
+  if (c.b.waves == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sha256_batch<true>, dim3(c.b.waves), dim3(64), 0, s, c);
   return hipGetLastError();
 }
 
