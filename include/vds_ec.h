@@ -381,6 +381,71 @@ int vds_ec_save_temp16_host_batch(uint16_t k, uint32_t n, uint32_t count, const 
                                   const uint64_t *sizes, uint8_t *const *outs, uint8_t *replica_digests,
                                   uint8_t *data_digests, uint32_t *replica_sizes);
 
+/* ------------------------------------------- wire text on the device
+ * The bodies of "upload" arrive as base64 and "download" answers in base64
+ * (websocket_api.cpp:141-155, :193); vds_ec_base64_decode / _encode above walk
+ * one text a character at a time on the calling thread, which costs more than
+ * everything save_temp does after it.  These decode and encode a BATCH of
+ * texts of different lengths in ONE launch each.
+ * Decode: text o is text_lens[o] characters at texts[o], its bytes go to
+ * outs[o] (texts, text_lens, outs, out_sizes: HOST arrays of `count`; the
+ * texts and outputs are device memory, any alignment -- the fast path is a
+ * 16-byte aligned text and a 4-byte aligned output).  out_sizes[o] is what
+ * vds_ec_base64_decoded_size gives for the text: the caller had the text in
+ * host memory before copying it over, and needs that size to allocate.
+ * statuses[o] (device, `count` int32_t) receives what vds_ec_base64_decode
+ * returns for the text -- VDS_EC_OK, VDS_EC_EB64_LENGTH, VDS_EC_EB64_PADDING,
+ * VDS_EC_EB64_CHAR, quirks as there: the first '=' ends the decode, the bytes
+ * it leaves unwritten are zero -- or VDS_EC_EINVAL when out_sizes[o] disagrees
+ * with the '=' among the text's last two characters (its output untouched).
+ * With VDS_EC_OK all out_sizes[o] bytes equal the host function's; with any
+ * other status the contents of the output are unspecified; either way no byte
+ * outside [outs[o], outs[o] + out_sizes[o]) is written, and only the aligned
+ * 4-byte words holding a character of a text are read.  Every status is
+ * written by the launch.  One wave walks one message (a text of many MiB is
+ * slow; the shape that matters is bodies of up to 64 KiB by the thousand); the
+ * descriptors ride the pinned parameter ring, longest message first.
+ * Every argument is validated before anything is enqueued and before the
+ * device is looked for (null arrays with count > 0, a null text or output
+ * where a length is non-zero, count >= 2^30, text_lens[o] >= 2^32,
+ * out_sizes[o] not one of len/4*3 - p for p = 0, 1, 2 or non-zero when
+ * len % 4 != 0: VDS_EC_EINVAL); count == 0 is VDS_EC_OK.  Nothing
+ * synchronises.                                                              */
+int vds_ec_base64_decode_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
+                                      uint8_t *const *outs, const uint64_t *out_sizes, int32_t *statuses,
+                                      void *stream);
+/* Encode (base64::from_bytes: standard alphabet, '=' padding, no NUL): input o
+ * is lens[o] bytes at ins[o], outs[o] receives (lens[o] + 2) / 3 * 4
+ * characters; same conventions (HOST arrays of device pointers, any alignment,
+ * only the outputs' own bytes written; lens[o] >= 2^32 or more than 2^31 - 1
+ * tiles of 6 KiB over the batch: VDS_EC_EINVAL).  Tiled over the whole batch,
+ * so a long input is split across waves.  In the download loop it follows
+ * vds_ec_restore16_batch_device on the same stream.                          */
+int vds_ec_base64_encode_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                      char *const *outs, void *stream);
+/* vds_ec_save_temp16_host_batch fed with TEXTS: text o (host, text_lens[o]
+ * characters of base64) is decoded on the device and its body encoded and
+ * named as there.  statuses[o] (host, required) receives the text's
+ * vds_ec_base64_decode status.  A message whose status is non-zero has none of
+ * its outputs written -- replicas outs[o*n + i], names, body hash,
+ * replica_sizes[o], bodies[o], body_sizes[o] --; *failed counts them; the call
+ * itself returns VDS_EC_OK.  bodies (when non-NULL: count host buffers of
+ * vds_ec_base64_decoded_size bytes) receive the decoded bodies, body_sizes
+ * their sizes.  replica_sizes, bodies, body_sizes, data_digests and failed may
+ * be NULL.  Works through groups of at most 64 MiB of text: texts gathered at
+ * 16-byte aligned offsets of pinned staging, one copy to the device, the
+ * decode launch into 16-byte aligned bodies, vds_ec_save_temp16_batch_device
+ * on those, one copy back of replicas, names, body hashes, statuses and (when
+ * asked for) bodies, scattered to the caller.  Sizes come from the host texts,
+ * so nothing waits for the decode; a text whose length is no multiple of 4
+ * gets no device work.  One device (the calling thread's current one);
+ * validation as the decode's and save_temp's, every message before any
+ * transfer.                                                                  */
+int vds_ec_upload16_host_batch(uint16_t k, uint32_t n, uint32_t count, const char *const *texts,
+                               const uint64_t *text_lens, uint8_t *const *outs, uint8_t *replica_digests,
+                               uint8_t *data_digests, uint32_t *replica_sizes, uint8_t *const *bodies,
+                               uint64_t *body_sizes, int32_t *statuses, uint32_t *failed);
+
 /* ------------------------------------------- repair loop and the name check
  * As vds_ec_sha256_batch_device, and message j's digest compared with
  * expected + 32*j (device, any alignment): verdicts[j] = 0 equal / 1

@@ -99,6 +99,11 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vds_ec_repair16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, u16p, vpp, u64p, C.c_uint32, u16p, vpp,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "vds_ec_base64_decode_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, C.c_void_p, C.c_void_p]),
+    "vds_ec_base64_encode_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, C.c_void_p]),
+    "vds_ec_upload16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, C.c_uint32, vpp, u64p, vpp, C.c_void_p,
+                                             C.c_void_p, C.POINTER(C.c_uint32), vpp, u64p, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_uint32)]),
     "vds_ec_base64_decoded_size": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "vds_ec_base64_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "vds_ec_base64_encode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -33,6 +33,7 @@ __all__ = [
     "regenerate_device", "sha256_device", "encode_hash_host", "replica_storage_paths",
     "VdsEcError", "multipliers", "inverse", "encode_range_device", "restore_range_device", "encode_host_split",
     "restore_host_split", "sha256_batch_device", "save_temp_batch_device", "save_temp_batch",
+    "base64_decode_batch_device", "base64_encode_batch_device", "upload_batch",
 ]
 
 
@@ -631,11 +632,88 @@ def save_temp(k: int, n: int, body):
 def upload(req_id: int, body_b64, k: int = 32, n: int = 64):
     """The live upload end to end: websocket "upload" body (base64) ->
     replicas, tmp-file names and the JSON answer (MIN_HORCRUX = 32,
-    GENERATE_HORCRUX = 64 by default, dht_network.h:22-25)."""
+    GENERATE_HORCRUX = 64 by default, dht_network.h:22-25).  One body, its
+    text decoded on the calling thread; a batch of bodies goes through
+    upload_batch, which decodes the texts on the device."""
     body = base64_decode(body_b64)
     reps, names, data_hash, rsize = save_temp(k, n, body)
     return {"replicas": reps, "tmp_names": tmp_names(names), "replica_digests": names, "data_hash": data_hash,
             "json": upload_response_json(req_id, names, data_hash, rsize)}
+
+
+def base64_decode_batch_device(texts, text_lens, outs, out_sizes, statuses, stream=None) -> None:
+    """vds_ec_base64_decode_batch_device: len(text_lens) base64 texts of
+    different lengths decoded in one launch -- text o is text_lens[o]
+    characters at the device pointer texts[o], its out_sizes[o] bytes (what
+    vds_ec_base64_decoded_size gives for the text) go to the device pointer
+    outs[o]; statuses (device, one int32 a text) receives what base64_decode
+    would return for each."""
+    tp = np.ascontiguousarray(np.asarray(texts, dtype=np.uint64).reshape(-1))
+    tl = np.ascontiguousarray(np.asarray(text_lens, dtype=np.uint64).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    os_ = np.ascontiguousarray(np.asarray(out_sizes, dtype=np.uint64).reshape(-1))
+    if not (tp.size == tl.size == op.size == os_.size):
+        raise VdsEcError(_lib.EINVAL, "base64_decode_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_base64_decode_batch_device(tl.size, tp.ctypes.data_as(_lib.vpp),
+                                                       tl.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+                                                       os_.ctypes.data_as(_lib.u64p), _dev_ptr(statuses),
+                                                       _stream_ptr(stream)), "base64_decode_batch_device")
+
+
+def base64_encode_batch_device(ins, lens, outs, stream=None) -> None:
+    """vds_ec_base64_encode_batch_device: input o, lens[o] bytes at the device
+    pointer ins[o], as (lens[o] + 2) // 3 * 4 characters of base64 at the
+    device pointer outs[o]; the whole batch in one launch."""
+    ip = np.ascontiguousarray(np.asarray(ins, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ln.size == op.size):
+        raise VdsEcError(_lib.EINVAL, "base64_encode_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_base64_encode_batch_device(ln.size, ip.ctypes.data_as(_lib.vpp),
+                                                       ln.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+                                                       _stream_ptr(stream)), "base64_encode_batch_device")
+
+
+def upload_batch(req_ids: Sequence[int], texts: Sequence, k: int = 32, n: int = 64, bodies: bool = False) -> list:
+    """vds_ec_upload16_host_batch: the live upload for a batch of websocket
+    "upload" bodies (base64 texts), decoded, encoded and named on the device.
+    Per message either what upload() returns (with "body", the decoded body,
+    when bodies is set) or, for a malformed text, the reference's error text."""
+    raws = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    count = len(raws)
+    if len(req_ids) != count:
+        raise VdsEcError(_lib.EINVAL, "upload_batch: one request id per text")
+    lib = _lib.lib()
+    tl = np.asarray([len(r) for r in raws], dtype=np.uint64)
+    sizes = [lib.vds_ec_base64_decoded_size(r, len(r)) for r in raws]
+    Ls = [replica_size(k, s) for s in sizes]
+    outs = [[np.empty(max(L, 1), dtype=np.uint8) for _ in range(n)] for L in Ls]
+    rd = np.empty((max(1, count * n), 32), dtype=np.uint8)
+    dd = np.empty((max(1, count), 32), dtype=np.uint8)
+    rs = np.zeros(max(1, count), dtype=np.uint32)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    bs = np.zeros(max(1, count), dtype=np.uint64)
+    bufs = [np.empty(max(s, 1), dtype=np.uint8) for s in sizes] if bodies else None
+    failed = C.c_uint32(0)
+    tp = (C.c_char_p * max(1, count))(*raws)
+    op = (C.c_void_p * max(1, count * n))(*[o.ctypes.data for os_ in outs for o in os_])
+    bp = (C.c_void_p * max(1, count))(*[b.ctypes.data for b in bufs]) if bodies else None
+    check(lib.vds_ec_upload16_host_batch(k, n, count, C.cast(tp, _lib.vpp), tl.ctypes.data_as(_lib.u64p), op,
+                                         rd.ctypes.data, dd.ctypes.data, rs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         bp, bs.ctypes.data_as(_lib.u64p), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         C.byref(failed)), "upload16_host_batch")
+    res = []
+    for o in range(count):
+        if st[o]:
+            res.append(_lib.strerror(int(st[o])))
+            continue
+        names = [bytes(x) for x in rd[o * n:(o + 1) * n]]
+        r = {"replicas": [x[:Ls[o]] for x in outs[o]], "tmp_names": tmp_names(names), "replica_digests": names,
+             "data_hash": bytes(dd[o]), "json": upload_response_json(req_ids[o], names, bytes(dd[o]), int(rs[o]))}
+        if bodies:
+            r["body"] = bytes(bufs[o][:int(bs[o])])
+        res.append(r)
+    return res
 
 
 def restore_path(k: int, nodes: Sequence[int], chunk_size: int, padding: int = 0, count: int = 1) -> int:

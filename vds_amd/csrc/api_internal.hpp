@@ -12,6 +12,8 @@
 //                       the batched save_temp built on it (device and host);
 //                       its check mode and the batched repair (regenerate,
 //                       name, check);
+//   api_upload_batch.cpp  base64 wire text decoded and encoded on the device,
+//                       and the batched upload from text (decode, save_temp);
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -127,6 +129,42 @@ struct PinnedRegistry {
   std::map<uintptr_t, PinnedRange> ranges;  // by start address
 };
 
+// Per (thread, device) staging of the host form: pinned and device buffers
+// for one group each way, and a stream.  Kept across calls (hipHostMalloc of
+// tens of MiB costs more than the group it feeds); never freed, as the other
+// host contexts (at process exit it would race the HIP runtime's teardown).
+struct SaveTempStage {
+  hipStream_t stream = nullptr;
+  uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+  size_t in_cap = 0, out_cap = 0;
+  int reserve(size_t in_b, size_t out_b) {
+    if (!stream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return VDS_EC_ENODEV;
+    if (in_b > in_cap) {
+      if (h_in) (void)hipHostFree(h_in);
+      if (d_in) (void)hipFree(d_in);
+      h_in = d_in = nullptr;
+      in_cap = 0;
+      if (hipHostMalloc(&h_in, in_b, 0) != hipSuccess || hipMalloc(&d_in, in_b) != hipSuccess) return VDS_EC_ENOMEM;
+      in_cap = in_b;
+    }
+    if (out_b > out_cap) {
+      if (h_out) (void)hipHostFree(h_out);
+      if (d_out) (void)hipFree(d_out);
+      h_out = d_out = nullptr;
+      out_cap = 0;
+      if (hipHostMalloc(&h_out, out_b, 0) != hipSuccess || hipMalloc(&d_out, out_b) != hipSuccess)
+        return VDS_EC_ENOMEM;
+      out_cap = out_b;
+    }
+    return VDS_EC_OK;
+  }
+};
+
+SaveTempStage *save_temp_stage();
+// a group's bound: api_host_batch.cpp's 64 MiB of input, and a count that keeps its tables small
+constexpr uint64_t kSaveTempGroupBytes = 64ull << 20;
+constexpr uint32_t kSaveTempGroupObjects = 1u << 16;
+
 int hip_status(hipError_t e);
 int device_ready();
 int inverse16(uint32_t k, const uint16_t *nodes, uint16_t *out);
@@ -172,6 +210,14 @@ int repair_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, const
 int repair_host_batch(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
                       const uint64_t *chunk_sizes, uint32_t nt, const uint16_t *targets, uint8_t *const *outs,
                       uint8_t *digests, const uint8_t *expected, uint8_t *verdicts, uint32_t *mismatches);
+// base64 wire text on the device (api_upload_batch.cpp, base64.hip)
+int base64_decode_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
+                               uint8_t *const *outs, const uint64_t *out_sizes, int32_t *statuses, hipStream_t s);
+int base64_encode_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, char *const *outs,
+                               hipStream_t s);
+int upload_host_batch(uint32_t k, uint32_t n, uint32_t count, const char *const *texts, const uint64_t *text_lens,
+                      uint8_t *const *outs, uint8_t *replica_digests, uint8_t *data_digests, uint32_t *replica_sizes,
+                      uint8_t *const *bodies, uint64_t *body_sizes, int32_t *statuses, uint32_t *failed);
 hipError_t param_acquire_n(int cnt, const size_t *bytes, ParamSlot **out);
 hipError_t param_commit(ParamSlot *sl, size_t bytes, hipStream_t s);
 hipError_t param_release(ParamSlot *sl, hipStream_t s);

@@ -234,39 +234,6 @@ int save_temp_batch_device(uint32_t k, uint32_t n, uint32_t count, const uint8_t
 }
 
 // ------------------------------------------------------------ host form
-namespace {
-
-// Per (thread, device) staging of the host form: pinned and device buffers
-// for one group each way, and a stream.  Kept across calls (hipHostMalloc of
-// tens of MiB costs more than the group it feeds); never freed, as the other
-// host contexts (at process exit it would race the HIP runtime's teardown).
-struct SaveTempStage {
-  hipStream_t stream = nullptr;
-  uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-  size_t in_cap = 0, out_cap = 0;
-  int reserve(size_t in_b, size_t out_b) {
-    if (!stream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return VDS_EC_ENODEV;
-    if (in_b > in_cap) {
-      if (h_in) (void)hipHostFree(h_in);
-      if (d_in) (void)hipFree(d_in);
-      h_in = d_in = nullptr;
-      in_cap = 0;
-      if (hipHostMalloc(&h_in, in_b, 0) != hipSuccess || hipMalloc(&d_in, in_b) != hipSuccess) return VDS_EC_ENOMEM;
-      in_cap = in_b;
-    }
-    if (out_b > out_cap) {
-      if (h_out) (void)hipHostFree(h_out);
-      if (d_out) (void)hipFree(d_out);
-      h_out = d_out = nullptr;
-      out_cap = 0;
-      if (hipHostMalloc(&h_out, out_b, 0) != hipSuccess || hipMalloc(&d_out, out_b) != hipSuccess)
-        return VDS_EC_ENOMEM;
-      out_cap = out_b;
-    }
-    return VDS_EC_OK;
-  }
-};
-
 SaveTempStage *save_temp_stage() {
   thread_local std::vector<SaveTempStage *> per_device;
   int dev = 0;
@@ -275,12 +242,6 @@ SaveTempStage *save_temp_stage() {
   if (!per_device[dev]) per_device[dev] = new SaveTempStage();
   return per_device[dev];
 }
-
-// a group's bound: api_host_batch.cpp's 64 MiB of input, and a count that keeps its tables small
-constexpr uint64_t kSaveTempGroupBytes = 64ull << 20;
-constexpr uint32_t kSaveTempGroupObjects = 1u << 16;
-
-}  // namespace
 
 int save_temp_host_batch(uint32_t k, uint32_t n, uint32_t count, const uint8_t *const *objs, const uint64_t *sizes,
                          uint8_t *const *outs, uint8_t *replica_digests, uint8_t *data_digests,

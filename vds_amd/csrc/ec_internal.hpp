@@ -147,6 +147,30 @@ struct ShaBatchCheckLaunch {
   const ShaBatchCheck *checks;
 };
 
+// base64 wire text (base64.hip).  Decode: one wave per message, the messages
+// longest first; msgs[w] is wave w's.  A step of a wave is kB64DecStep
+// characters (16 a lane).
+constexpr uint32_t kB64DecStep = 1024;
+struct B64DecMsg {
+  uint64_t text;    // len characters, any alignment
+  uint64_t out;     // size bytes, any alignment
+  uint64_t status;  // its int32_t status (VDS_EC_OK, VDS_EC_EB64_*, VDS_EC_EINVAL), 4-byte aligned
+  uint32_t len;
+  uint32_t size;    // declared: len / 4 * 3 - p, p = 0, 1, 2 (0 when len % 4)
+};
+// Encode: one wave per tile of kB64EncTile input bytes (8 steps of 12 bytes a
+// lane), tiles[w] = wave w's message and its tile of it.
+constexpr uint32_t kB64EncTile = 6144;
+struct B64EncMsg {
+  uint64_t in;   // len bytes, any alignment
+  uint64_t out;  // (len + 2) / 3 * 4 characters, any alignment
+  uint64_t len;
+};
+struct B64EncTile {
+  uint32_t msg;
+  uint32_t tile;
+};
+
 // Bit-sliced runtime-coefficient restore over 512-stripe groups: the first
 // groups_per_obj groups of every object as one stream of 4-group tiles.
 struct FastRestoreArgs {
@@ -391,6 +415,10 @@ hipError_t launch_sha256(const uint8_t *base, uint64_t len, uint64_t stride, uin
 hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s);
 // The same, and every group's check (ShaBatchCheck) in the same launch.
 hipError_t launch_sha256_check_batch(const ShaBatchCheckLaunch &c, hipStream_t s);
+// base64 -> bytes of msgs[0..count) (device table), every status written (base64.hip).
+hipError_t launch_b64_decode_batch(const B64DecMsg *msgs, uint32_t count, hipStream_t s);
+// bytes -> base64 over tiles[0..ntiles) of msgs (device tables).
+hipError_t launch_b64_encode_batch(const B64EncMsg *msgs, const B64EncTile *tiles, uint32_t ntiles, hipStream_t s);
 hipError_t launch_fill_splitmix(uint8_t *dst, uint64_t size, uint64_t seed, hipStream_t s);
 // Device -> mapped pinned host copy by a kernel (dst: the device view of the
 // host buffer; both 16-byte aligned).
