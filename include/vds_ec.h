@@ -45,6 +45,8 @@ extern "C" {
 #define VDS_EC_EB64_LENGTH (-7)  /* "Non-Valid base64!" (length % 4 != 0)      */
 #define VDS_EC_EB64_PADDING (-8) /* "Invalid Padding in Base 64!"              */
 #define VDS_EC_EB64_CHAR (-9)    /* "Non-Valid Character in Base 64!"          */
+/* a replica's bytes do not hash to its name (read_data, dht_network_client.cpp:952-960): */
+#define VDS_EC_ECORRUPT (-10)    /* "Data is corrupted"                        */
 
 /* ----------------------------------------------------------------- flags */
 /* write_padding = false in chunk_generator::write (chunk.h:79,273-278):
@@ -508,6 +510,107 @@ int vds_ec_repair16_host_batch(uint16_t k, uint32_t count, const uint16_t *nodes
                                const uint64_t *chunk_sizes, uint32_t ntargets, const uint16_t *targets,
                                uint8_t *const *outs, uint8_t *digests, const uint8_t *expected,
                                uint8_t *verdicts, uint32_t *mismatches);
+
+/* ------------------------------------------------------------ download loop
+ * vds_ec_base64_encode_batch_device behind a gate: message o also carries
+ * gates[o] (device, ngates[o] verdict bytes of an earlier launch on the same
+ * stream, any alignment; ngates[o] == 0: ungated, gates[o] not read) and the
+ * status slot statuses + o (device, `count` int32_t).  A wave ORs the
+ * message's gate bytes before it writes anything; with any of them non-zero
+ * NO character of the message is written and its status is VDS_EC_ECORRUPT,
+ * else the text is the ungated call's and the status VDS_EC_OK.  Every status
+ * is written by the launch, a message of length 0 included.  Conventions and
+ * validation as the ungated call's (every message counts at least one tile),
+ * and null gates, ngates or statuses with count > 0, a null gates[o] where
+ * ngates[o] != 0: VDS_EC_EINVAL.  Nothing synchronises; stream order is the
+ * only ordering between the launch that wrote the gate bytes and this one.   */
+int vds_ec_base64_encode_gated_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                            char *const *outs, const uint8_t *const *gates, const uint32_t *ngates,
+                                            int32_t *statuses, void *stream);
+/* The download loop (websocket_api.cpp:191-210 -> restore_async,
+ * dht_network_client.cpp:851-901 -> the base64 answer, websocket_api.cpp:772-782)
+ * for a batch, CHECKED: on the one stream, in this order,
+ *   1. the check of the names the request carries (websocket_api.cpp:193),
+ *   2. vds_ec_restore16_batch_device into objects[o] (same arguments, same
+ *      planning, same bytes, every route),
+ *   3. one gated encode of object o's E = vds_ec_restored_size(2, k,
+ *      chunk_sizes[o], paddings[o]) bytes into (E + 2) / 3 * 4 characters at
+ *      texts[o] (device, any alignment), gated by the object's verdict bytes:
+ *      statuses[o] (device, `count` int32_t) is VDS_EC_OK and the text is
+ *      written, or VDS_EC_ECORRUPT and no character of it is.
+ * HOST arrays of device pointers, as vds_ec_restore16_batch_device takes them.
+ * Exactly one check is given (both or neither: VDS_EC_EINVAL):
+ *   SURVIVOR MODE, survivor_names != NULL (device, count*k*32 bytes, the name
+ *   of survivor chunks[o*k + j] at 32*(o*k + j)):
+ *   vds_ec_sha256_check_batch_device's launch over the count*k survivors
+ *   (check only; planned as one group an object, 1/k of the descriptors);
+ *   verdicts (device) holds count*k bytes, object o's gate is its k bytes.
+ *   Covers EVERY BYTE OF EVERY SURVIVOR, trailers included -- stricter than
+ *   the reference's route, which reads the first survivor's trailer only.
+ *   WITNESS MODE, witness_ids (HOST, count ids), witness_names (device,
+ *   count*32) and witness_outs (HOST array of count device buffers of
+ *   chunk_sizes[o] bytes) all given: replica witness_ids[o] of object o -- one
+ *   that is not among its survivors -- is regenerated into witness_outs[o] and
+ *   its name compared with witness_names + 32*o, the two launches of
+ *   vds_ec_repair16_batch_device with ntargets = 1 (the witness's digest is
+ *   compared inside the hash launch and stored nowhere); verdicts holds count
+ *   bytes, object o's gate is its one byte.  Covers EVERY CELL OF EVERY
+ *   SURVIVOR and the FIRST survivor's trailer: the code is MDS, so changing
+ *   any cell of any of the k survivors changes that stripe's cell in every
+ *   other replica, the witness included -- at 1/k of the hashing.  The
+ *   reference route reads no trailer but the first survivor's (chunk.h:408),
+ *   so a wrong trailer on survivor 2..k leaves the witness, the verdict and
+ *   the restored object unchanged.  Of a partial last stripe the route keeps
+ *   the object's own bytes only (chunk.h:415-419): a changed cell there whose
+ *   decode differs in the trimmed bytes alone regenerates the same witness
+ *   and restores the same object, and passes with the exact text (survivor
+ *   mode fails it: the file is not the named one).  A first trailer above 2k leaves the
+ *   witness unspecified (see vds_ec_regenerate16_device); a valid upload never
+ *   has one (p = S mod 2k), and the host form below handles it.
+ * Every argument is validated before anything is enqueued and before the
+ * device is looked for: restore's checks (VDS_EC_ERESTORE, VDS_EC_ESINGULAR
+ * included), the name check's, with a witness repair's (chunk sizes of whole
+ * cells and a trailer, VDS_EC_ESINGULAR whatever the size) and a witness id
+ * equal to one of its object's survivor ids (VDS_EC_EINVAL); null arrays with
+ * count > 0, a null objects[o] or texts[o] where E != 0, E >= 2^32,
+ * count >= 2^30, count*(k + 64) >= 2^32 (survivor mode) or count*65 >= 2^32
+ * (witness mode; the hash launch's lanes): VDS_EC_EINVAL.  count == 0 is VDS_EC_OK.  Nothing synchronises.
+ * Only the objects', texts', witnesses', verdicts' and statuses' own bytes
+ * are written.                                                               */
+int vds_ec_download16_batch_device(uint16_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                                   const uint64_t *chunk_sizes, const uint16_t *paddings,
+                                   const uint8_t *survivor_names, const uint16_t *witness_ids,
+                                   const uint8_t *witness_names, uint8_t *const *witness_outs,
+                                   uint8_t *const *objects, char *const *texts, uint8_t *verdicts, int32_t *statuses,
+                                   void *stream);
+/* The same from and to host memory on the calling thread's current device:
+ * survivors chunks[o*k + j] (chunk_sizes[o] host bytes; whole cells and a
+ * trailer), their names survivor_names (host, count*k*32, REQUIRED in both
+ * modes), and, for witness mode, witness_ids and witness_names (host, count
+ * ids and count*32 bytes; both NULL: survivor mode).  texts[o] (host) receives
+ * the base64 text, text_lens[o] holds its capacity on entry (less than the
+ * text needs: VDS_EC_EINVAL) and its length on return; statuses[o] (host,
+ * count) the object's status; survivor_verdicts (host, count*k bytes) which
+ * survivors' names did not match.  A failed object's text is untouched and
+ * its text_lens[o] is 0; *failed (may be NULL) counts them; the call itself
+ * returns VDS_EC_OK.  Paddings come from the first chunk's trailer.
+ * Works through groups of at most 64 MiB of survivor bytes: survivors
+ * gathered into pinned staging with the names, one copy to the device, the
+ * call above, one copy back of texts and statuses (and, in survivor mode, the
+ * gate, which is survivor_verdicts).  In witness mode the survivors of the
+ * objects whose status came back non-zero, still on the device, get one more
+ * vds_ec_sha256_check_batch_device launch, theirs alone, which LOCATES the
+ * rotten file: their survivor_verdicts come from it (all zero: the names
+ * match and the first trailer is wrong within 2k, or the witness's name is);
+ * objects that passed get zeros.  An object whose first trailer has no answer
+ * gets no restore and goes straight to that pass: above 2k in witness mode
+ * (VDS_EC_ECORRUPT), restore's "Fatal error" in survivor mode
+ * (VDS_EC_ERESTORE).  Validation as above, every object before any transfer.  */
+int vds_ec_download16_host_batch(uint16_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                                 const uint64_t *chunk_sizes, const uint8_t *survivor_names,
+                                 const uint16_t *witness_ids, const uint8_t *witness_names, char *const *texts,
+                                 uint64_t *text_lens, int32_t *statuses, uint8_t *survivor_verdicts,
+                                 uint32_t *failed);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

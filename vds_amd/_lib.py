@@ -22,6 +22,7 @@ EHIP = -6
 EB64_LENGTH = -7
 EB64_PADDING = -8
 EB64_CHAR = -9
+ECORRUPT = -10
 
 F_NO_TRAILER = 0x1
 F_CELLS = 0x2
@@ -104,6 +105,13 @@ SIGNATURES = {
     "vds_ec_upload16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, C.c_uint32, vpp, u64p, vpp, C.c_void_p,
                                              C.c_void_p, C.POINTER(C.c_uint32), vpp, u64p, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_uint32)]),
+    "vds_ec_base64_encode_gated_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, vpp, C.POINTER(C.c_uint32),
+                                                          C.c_void_p, C.c_void_p]),
+    "vds_ec_download16_batch_device": (C.c_int, [C.c_uint16, C.c_uint32, u16p, vpp, u64p, u16p, C.c_void_p, u16p,
+                                                 C.c_void_p, vpp, vpp, vpp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vds_ec_download16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, u16p, vpp, u64p, C.c_void_p, u16p,
+                                               C.c_void_p, vpp, u64p, C.POINTER(C.c_int32), C.c_void_p,
+                                               C.POINTER(C.c_uint32)]),
     "vds_ec_base64_decoded_size": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "vds_ec_base64_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "vds_ec_base64_encode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -34,6 +34,7 @@ __all__ = [
     "VdsEcError", "multipliers", "inverse", "encode_range_device", "restore_range_device", "encode_host_split",
     "restore_host_split", "sha256_batch_device", "save_temp_batch_device", "save_temp_batch",
     "base64_decode_batch_device", "base64_encode_batch_device", "upload_batch",
+    "base64_encode_gated_batch_device", "download_batch_device", "download_batch",
 ]
 
 
@@ -503,6 +504,101 @@ def repair_batch(k: int, horcruxes: Sequence[Mapping[int, object]], targets: Seq
                                                 C.byref(bad)), "repair16_host_batch")
     return [([r[:int(cs[o])] for r in outs[o]], [bytes(x) for x in dg[o * nt:(o + 1) * nt]],
              None if vd is None else [int(v) for v in vd[o * nt:(o + 1) * nt]]) for o in range(count)]
+
+
+def base64_encode_gated_batch_device(ins, lens, outs, gates, ngates, statuses, stream=None) -> None:
+    """vds_ec_base64_encode_gated_batch_device: base64_encode_batch_device
+    behind verdict bytes -- message o is written only when its ngates[o] bytes
+    at the device pointer gates[o] are all zero; statuses (device, one int32 a
+    message) receives 0 or ECORRUPT for every message."""
+    ip = np.ascontiguousarray(np.asarray(ins, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    gp = np.ascontiguousarray(np.asarray(gates, dtype=np.uint64).reshape(-1))
+    ng = np.ascontiguousarray(np.asarray(ngates, dtype=np.uint32).reshape(-1))
+    if not (ip.size == ln.size == op.size == gp.size == ng.size):
+        raise VdsEcError(_lib.EINVAL, "base64_encode_gated_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_base64_encode_gated_batch_device(ln.size, ip.ctypes.data_as(_lib.vpp),
+                                                             ln.ctypes.data_as(_lib.u64p),
+                                                             op.ctypes.data_as(_lib.vpp),
+                                                             gp.ctypes.data_as(_lib.vpp),
+                                                             ng.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                             _dev_ptr(statuses), _stream_ptr(stream)),
+          "base64_encode_gated_batch_device")
+
+
+def download_batch_device(k: int, nodes: Sequence[Sequence[int]], chunks: Sequence[Sequence[int]],
+                          chunk_sizes: Sequence[int], paddings: Sequence[int], objects: Sequence[int],
+                          texts: Sequence[int], verdicts, statuses, survivor_names=None, witness_ids=None,
+                          witness_names=None, witness_outs=None, stream=None) -> None:
+    """vds_ec_download16_batch_device: the name check, restore_batch_device into
+    the device pointers objects[o] and the gated base64 encode into the device
+    pointers texts[o], on one stream.  Survivor mode: survivor_names (device,
+    32 bytes a survivor), verdicts k bytes an object.  Witness mode:
+    witness_ids[o], witness_names (device, 32 bytes an object) and the device
+    pointers witness_outs[o], verdicts one byte an object.  statuses (device,
+    one int32 an object) receives 0 or ECORRUPT."""
+    count = len(nodes)
+    ids = _ids([r for nd in nodes for r in nd], 2)
+    cp = (C.c_void_p * max(1, count * k))(*[int(c) for ch in chunks for c in ch])
+    cs = np.asarray(chunk_sizes, dtype=np.uint64)
+    pd = np.asarray(paddings, dtype=np.uint16)
+    ob = (C.c_void_p * max(1, count))(*[int(o) or None for o in objects])
+    tp = (C.c_void_p * max(1, count))(*[int(t) or None for t in texts])
+    wi = _ids(witness_ids, 2) if witness_ids is not None else None
+    wo = (C.c_void_p * max(1, count))(*[int(w) for w in witness_outs]) if witness_outs is not None else None
+    check(_lib.lib().vds_ec_download16_batch_device(k, count, _idp(ids, 2), cp, cs.ctypes.data_as(_lib.u64p),
+                                                    pd.ctypes.data_as(_lib.u16p), _dev_ptr(survivor_names),
+                                                    _idp(wi, 2) if wi is not None else None,
+                                                    _dev_ptr(witness_names), wo, ob, tp, _dev_ptr(verdicts),
+                                                    _dev_ptr(statuses), _stream_ptr(stream)),
+          "download16_batch_device")
+
+
+def download_batch(k: int, horcruxes: Sequence[Mapping[int, object]], names: Sequence[Sequence[bytes]],
+                   witnesses: Sequence | None = None) -> list:
+    """vds_ec_download16_host_batch: the download loop for a batch of host
+    objects, checked.  horcruxes[o] maps replica id -> bytes (its first k
+    entries are used, in order), names[o] their k SHA-256 names; witnesses,
+    when given, holds per object (replica id, name) of one replica that is not
+    among them (witness mode: 1/k of the hashing).  Returns per object
+    (text or None, status, survivor verdicts): the base64 text of the restored
+    object when its status is 0."""
+    count = len(horcruxes)
+    items = [list(h.items())[:k] for h in horcruxes]
+    if any(len(it) < k for it in items) or len(names) != count or (witnesses is not None and len(witnesses) != count):
+        raise VdsEcError(_lib.EINVAL, "download_batch")
+    ids = _ids([r for it in items for r, _ in it], 2)
+    bufs = [[_u8(v) for _, v in it] for it in items]
+    if any(b.size != bs[0].size for bs in bufs for b in bs):
+        raise VdsEcError(_lib.EINVAL, "download_batch")
+    cs = np.asarray([bs[0].size for bs in bufs], dtype=np.uint64)
+    sn = np.ascontiguousarray(np.frombuffer(b"".join(bytes(x) for row in names for x in row), dtype=np.uint8))
+    if sn.size != 32 * count * k:
+        raise VdsEcError(_lib.EINVAL, "download_batch: names does not hold one name per survivor")
+    wi = wn = None
+    if witnesses is not None:
+        wi = _ids([w for w, _ in witnesses], 2)
+        wn = np.ascontiguousarray(np.frombuffer(b"".join(bytes(x) for _, x in witnesses), dtype=np.uint8))
+        if wn.size != 32 * count:
+            raise VdsEcError(_lib.EINVAL, "download_batch: one (id, name) per object")
+    caps = [(int(c) * k + 2) // 3 * 4 for c in cs]  # (E <= chunk_size * k)
+    outs = [C.create_string_buffer(max(1, c)) for c in caps]
+    tl = np.asarray(caps, dtype=np.uint64)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    sv = np.zeros(max(1, count * k), dtype=np.uint8)
+    failed = C.c_uint32(0)
+    cp = (C.c_void_p * max(1, count * k))(*[b.ctypes.data for bs in bufs for b in bs])
+    tp = (C.c_void_p * max(1, count))(*[C.addressof(o) for o in outs])
+    check(_lib.lib().vds_ec_download16_host_batch(k, count, _idp(ids, 2), cp, cs.ctypes.data_as(_lib.u64p),
+                                                  sn.ctypes.data if sn.size else None,
+                                                  _idp(wi, 2) if wi is not None and count else None,
+                                                  wn.ctypes.data if wn is not None and count else None, tp,
+                                                  tl.ctypes.data_as(_lib.u64p),
+                                                  st.ctypes.data_as(C.POINTER(C.c_int32)), sv.ctypes.data,
+                                                  C.byref(failed)), "download16_host_batch")
+    return [(None if st[o] else outs[o].raw[:int(tl[o])].decode(), int(st[o]),
+             [int(v) for v in sv[o * k:(o + 1) * k]]) for o in range(count)]
 
 
 def save_temp_batch_device(k: int, n: int, ins, sizes, outs, replica_digests, data_digests=None,

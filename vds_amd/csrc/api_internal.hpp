@@ -14,6 +14,9 @@
 //                       name, check);
 //   api_upload_batch.cpp  base64 wire text decoded and encoded on the device,
 //                       and the batched upload from text (decode, save_temp);
+//   api_download_batch.cpp  the download loop in one call: the name check
+//                       (survivors or a witness), the batched restore and the
+//                       gated base64 encode (device and host);
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -218,6 +221,21 @@ int base64_encode_batch_device(uint32_t count, const uint8_t *const *ins, const 
 int upload_host_batch(uint32_t k, uint32_t n, uint32_t count, const char *const *texts, const uint64_t *text_lens,
                       uint8_t *const *outs, uint8_t *replica_digests, uint8_t *data_digests, uint32_t *replica_sizes,
                       uint8_t *const *bodies, uint64_t *body_sizes, int32_t *statuses, uint32_t *failed);
+// the download loop (api_download_batch.cpp): check, restore, gated base64 encode
+int sha256_check_groups_device(uint32_t ngroups, uint32_t m, const uint8_t *const *msgs, const uint64_t *lens,
+                               const uint8_t *const *expected, uint8_t *const *verdicts, hipStream_t s);
+int base64_encode_gated_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                     char *const *outs, const uint8_t *const *gates, const uint32_t *ngates,
+                                     int32_t *statuses, hipStream_t s);
+int download_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                          const uint64_t *chunk_sizes, const uint16_t *paddings, const uint8_t *survivor_names,
+                          const uint16_t *witness_ids, const uint8_t *witness_names, uint8_t *const *witness_outs,
+                          uint8_t *const *objects, char *const *texts, uint8_t *verdicts, int32_t *statuses,
+                          hipStream_t s);
+int download_host_batch(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
+                        const uint64_t *chunk_sizes, const uint8_t *survivor_names, const uint16_t *witness_ids,
+                        const uint8_t *witness_names, char *const *texts, uint64_t *text_lens, int32_t *statuses,
+                        uint8_t *survivor_verdicts, uint32_t *failed);
 hipError_t param_acquire_n(int cnt, const size_t *bytes, ParamSlot **out);
 hipError_t param_commit(ParamSlot *sl, size_t bytes, hipStream_t s);
 hipError_t param_release(ParamSlot *sl, hipStream_t s);

@@ -341,6 +341,21 @@ int sha256_check_batch_device(uint32_t count, const uint8_t *const *msgs, const 
   return launch_sha_groups(sc, s);
 }
 
+// Check only, group by group (the download loop's second pass, over the
+// survivors of the objects that failed): group g is the m messages
+// msgs[g*m + i] of lens[g] bytes each, compared with expected[g] + 32 i into
+// verdicts[g] + i.  One launch.  The caller has validated the arguments and
+// found the device.
+int sha256_check_groups_device(uint32_t ngroups, uint32_t m, const uint8_t *const *msgs, const uint64_t *lens,
+                               const uint8_t *const *expected, uint8_t *const *verdicts, hipStream_t s) {
+  if (ngroups == 0 || m == 0) return VDS_EC_OK;
+  if ((uint64_t)ngroups * ((uint64_t)m + 64) > 0xFFFFFFFFull) return VDS_EC_EINVAL;
+  ShaBatchScratch &sc = sha_batch_scratch();
+  sc.clear(true);
+  for (uint32_t g = 0; g < ngroups; ++g) sc.add_ptrs(msgs + (uint64_t)g * m, m, lens[g], nullptr, expected[g], verdicts[g]);
+  return launch_sha_groups(sc, s);
+}
+
 namespace {
 
 // What the repair entry points check beyond vds_ec_regenerate16_batch_device

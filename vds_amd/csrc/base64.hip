@@ -25,6 +25,9 @@
 // k_b64_encode_batch: `count` inputs of different lengths, tiled over the whole
 // batch (kB64EncTile input bytes a wave, 12 a lane a step); nothing is
 // sequential, so long inputs are split across waves.
+// k_b64_encode_batch<true>: the same behind verdict bytes (the download
+// loop's check): a message whose gate bytes are not all zero gets no character
+// written and VDS_EC_ECORRUPT in its status slot.
 //
 // Both take texts, inputs and outputs at any byte address: only the aligned
 // 4-byte words holding at least one input byte are read, and only the output's
@@ -230,12 +233,29 @@ __device__ __forceinline__ uint32_t b64_chars(uint32_t t) {
          (b64_char(t & 63u) << 24);
 }
 
+// GATED (the download loop's last launch): gates[tl.msg] beside msgs[tl.msg].
+// Before it writes anything a wave ORs its message's ngate gate bytes (64 a
+// step, then one ballot over the wave); with any of them non-zero no tile of
+// the message writes a character.  The wave of the message's tile 0 -- every
+// message has one, an empty message too -- writes the status.  The gate bytes
+// come from an earlier launch on the same stream: stream order is all the
+// ordering needed.  Ungated, `gates` is not read and the kernel is the one it
+// was before the gate existed.
+template <bool GATED>
 __global__ __launch_bounds__(256) void k_b64_encode_batch(const B64EncMsg *msgs, const B64EncTile *tiles,
-                                                          uint32_t ntiles) {
+                                                          uint32_t ntiles, const B64EncGate *gates) {
   const uint32_t wv = blockIdx.x * 4u + threadIdx.x / 64u;
-  if (wv >= ntiles) return;
+  if (wv >= ntiles) return;  // (wave-uniform: every lane of a wave that goes on takes part in the ballot)
   const uint32_t lane = threadIdx.x % 64u;
   const B64EncTile tl = tiles[wv];
+  if constexpr (GATED) {
+    const B64EncGate g = gates[tl.msg];
+    uint32_t any = 0;
+    for (uint32_t i = lane; i < g.ngate; i += 64u) any |= byte_at(g.gate + i);
+    const bool shut = __ballot(any != 0) != 0ull;
+    if (tl.tile == 0 && lane == 0) *reinterpret_cast<gptr_wi32>(g.status) = shut ? VDS_EC_ECORRUPT : VDS_EC_OK;
+    if (shut) return;
+  }
   const B64EncMsg m = msgs[tl.msg];
   const uint64_t len = m.len;
   const uint32_t sh = (uint32_t)(m.in & 3u);
@@ -288,7 +308,15 @@ hipError_t launch_b64_decode_batch(const B64DecMsg *msgs, uint32_t count, hipStr
 
 hipError_t launch_b64_encode_batch(const B64EncMsg *msgs, const B64EncTile *tiles, uint32_t ntiles, hipStream_t s) {
   if (ntiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_b64_encode_batch, dim3((ntiles + 3) / 4), dim3(256), 0, s, msgs, tiles, ntiles);
+  hipLaunchKernelGGL(k_b64_encode_batch<false>, dim3((ntiles + 3) / 4), dim3(256), 0, s, msgs, tiles, ntiles,
+                     static_cast<const B64EncGate *>(nullptr));
+  return hipGetLastError();
+}
+
+hipError_t launch_b64_encode_gated_batch(const B64EncMsg *msgs, const B64EncGate *gates, const B64EncTile *tiles,
+                                         uint32_t ntiles, hipStream_t s) {
+  if (ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_b64_encode_batch<true>, dim3((ntiles + 3) / 4), dim3(256), 0, s, msgs, tiles, ntiles, gates);
   return hipGetLastError();
 }
 

@@ -170,6 +170,16 @@ struct B64EncTile {
   uint32_t msg;
   uint32_t tile;
 };
+// Gated encode (k_b64_encode_batch<true>): gates[m] beside msgs[m], and every
+// message has a tile 0 (a message of length 0 too).  A message whose ngate
+// gate bytes are not all zero has no character written; its tile 0 writes the
+// status either way.
+struct B64EncGate {
+  uint64_t gate;    // ngate bytes, any alignment (verdicts of an earlier launch on the stream); ngate == 0: never read
+  uint64_t status;  // its int32_t status (VDS_EC_OK, VDS_EC_ECORRUPT), 4-byte aligned
+  uint32_t ngate;
+  uint32_t reserved;
+};
 
 // Bit-sliced runtime-coefficient restore over 512-stripe groups: the first
 // groups_per_obj groups of every object as one stream of 4-group tiles.
@@ -419,6 +429,9 @@ hipError_t launch_sha256_check_batch(const ShaBatchCheckLaunch &c, hipStream_t s
 hipError_t launch_b64_decode_batch(const B64DecMsg *msgs, uint32_t count, hipStream_t s);
 // bytes -> base64 over tiles[0..ntiles) of msgs (device tables).
 hipError_t launch_b64_encode_batch(const B64EncMsg *msgs, const B64EncTile *tiles, uint32_t ntiles, hipStream_t s);
+// The same behind gates[0..) (beside msgs); every message's status written by its tile 0.
+hipError_t launch_b64_encode_gated_batch(const B64EncMsg *msgs, const B64EncGate *gates, const B64EncTile *tiles,
+                                         uint32_t ntiles, hipStream_t s);
 hipError_t launch_fill_splitmix(uint8_t *dst, uint64_t size, uint64_t seed, hipStream_t s);
 // Device -> mapped pinned host copy by a kernel (dst: the device view of the
 // host buffer; both 16-byte aligned).

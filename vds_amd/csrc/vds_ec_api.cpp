@@ -1014,6 +1014,7 @@ const char *vds_ec_strerror(int status) {
     case VDS_EC_EB64_LENGTH: return "Non-Valid base64!";
     case VDS_EC_EB64_PADDING: return "Invalid Padding in Base 64!";
     case VDS_EC_EB64_CHAR: return "Non-Valid Character in Base 64!";
+    case VDS_EC_ECORRUPT: return "Data is corrupted";
     default: return "unknown vds_ec status";
   }
 }
