@@ -47,6 +47,10 @@ extern "C" {
 #define VDS_EC_EB64_CHAR (-9)    /* "Non-Valid Character in Base 64!"          */
 /* a replica's bytes do not hash to its name (read_data, dht_network_client.cpp:952-960): */
 #define VDS_EC_ECORRUPT (-10)    /* "Data is corrupted"                        */
+/* the datagram layer (dht_datagram_protocol.cpp:130-141, :544-769), by the reference's text: */
+#define VDS_EC_EDGRAM_SIGNATURE (-11)  /* "Invalid signature"                   */
+#define VDS_EC_EDGRAM_DATA (-12)       /* "Invalid data"                        */
+#define VDS_EC_EDGRAM_INCOMPLETE (-13) /* a message whose datagrams are not all present and verified */
 
 /* ----------------------------------------------------------------- flags */
 /* write_padding = false in chunk_generator::write (chunk.h:79,273-278):
@@ -611,6 +615,145 @@ int vds_ec_download16_host_batch(uint16_t k, uint32_t count, const uint16_t *nod
                                  const uint16_t *witness_ids, const uint8_t *witness_names, char *const *texts,
                                  uint64_t *text_lens, int32_t *statuses, uint8_t *survivor_verdicts,
                                  uint32_t *failed);
+
+/* ------------------------------------------------ node-to-node transport
+ * A replica crosses between nodes as a sync_replica_data message
+ * (sync_process.cpp:184-191, messages/sync_messages.h:311-330) that
+ * dht_datagram_protocol::prepare_to_send (impl/dht_datagram_protocol.cpp:335-541)
+ * cuts into datagrams of at most mtu bytes, each signed with HMAC-SHA256
+ * (RFC 2104, OpenSSL's HMAC: kernel/vds_crypto/hash.cpp:218-260) under the
+ * 32-byte session key (udp_transport.cpp:275-276); the receiver verifies each
+ * (:130-141) and stitches the payloads together (:544-769).  These calls seal
+ * and open a ragged BATCH of messages in one launch each way.  Acknowledgment,
+ * resend, MTU probing, the handshake, the sockets and message dispatch stay
+ * with the caller: this layer takes and returns datagram bytes.
+ *
+ * Wire format (integers big-endian; R = the route blob of r bytes: r = 0
+ * direct, 32 the target id, 33 + 32 h target || h || h hop ids; M = the message
+ * of m bytes; i0 = the message's first datagram index; type < 32):
+ *   37 + r + m < mtu:  one datagram  B0 || BE32(i0) || R || M || MAC(all before),
+ *                      B0 = type | 0x20 (r = 0), 0x60 (r = 32), 0xA0 (proxy);
+ *   else the first is  B0 || BE32(i0) || BE32(m) || R || M[0, c0) || MAC with
+ *                      B0 = type | 0x40 / 0x80 / 0xC0 and c0 = mtu - (41 + r)
+ *                      (exactly mtu bytes), and continuation j = 1, 2, .. is
+ *                      0x03 || BE32(i0 + j) || the next min(mtu - 37, rest)
+ *                      bytes || MAC.
+ *
+ * HMAC-SHA256 of ONE host message on the calling thread (no GPU), any key
+ * length (a key longer than 64 bytes is hashed first), on
+ * vds_ec_sha256_host's compression.                                          */
+int vds_ec_hmac_sha256_host(const uint8_t *key, uint64_t key_len, const uint8_t *data, uint64_t len, uint8_t *mac);
+/* The sealing rules as host arithmetic (no GPU): *count datagrams, the first
+ * carrying *first_payload message bytes, the last *last_len bytes long in all
+ * (every other one is mtu bytes); any of the three may be NULL.  508 <= mtu <=
+ * 65535, route_len one of the three forms above (h < 256), 41 + route_len <
+ * mtu, msg_len < 2^32: VDS_EC_EINVAL otherwise.                              */
+int vds_ec_dgram_layout(uint32_t mtu, uint32_t route_len, uint64_t msg_len, uint32_t *count, uint32_t *first_payload,
+                        uint32_t *last_len);
+/* binary_serializer::write_number (binary_serialize.cpp:44-66), the length
+ * prefix of a serialized buffer: out receives *len <= 9 bytes.  With it a
+ * caller lays out a sync_replica_data body -- object_id, the prefix, the
+ * replica, owner, value_id, BE16(replica) -- around a gap of replica size and
+ * points vds_ec_repair16_batch_device's outs into the gap: the replica is
+ * never copied to build its message.                                         */
+int vds_ec_write_number(uint64_t value, uint8_t *out, uint32_t *len);
+/* HMAC-SHA256 of `count` device messages of different lengths in ONE launch,
+ * one lane per message: message j is lens[j] bytes at msgs[j] (HOST arrays of
+ * device pointers and lengths, any alignment, lens[j] == 0 allows NULL) under
+ * key session_of[j] of keys (HOST, nsessions keys of 32 bytes; the key pads
+ * are hashed on the host, once per session); MAC j goes to macs + 32*j
+ * (device; may be NULL when expected is given) and, with expected (device,
+ * count*32 bytes, any alignment), is compared into verdicts[j] (device; 0
+ * equal, 1 different).  expected and verdicts are NULL together.  The lanes are
+ * ordered by length on the host.  Every argument is validated before anything
+ * is enqueued and before the device is looked for (null arrays, a null message
+ * with a non-zero length, session_of[j] >= nsessions, lens[j] > 2^30,
+ * count >= 2^30: VDS_EC_EINVAL); count == 0 is VDS_EC_OK.  Nothing
+ * synchronises; the tables ride the pinned parameter ring.                   */
+int vds_ec_hmac_sha256_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
+                                    const uint32_t *session_of, const uint8_t *keys, uint32_t nsessions,
+                                    uint8_t *macs, const uint8_t *expected, uint8_t *verdicts, void *stream);
+/* Seal `count` messages, one lane per DATAGRAM: message o (msg_lens[o] device
+ * bytes at msgs[o], any alignment) of type types[o], first index index0[o],
+ * route blob routes[o] (route_lens[o] device bytes; routes may be NULL when
+ * every length is 0), session session_of[o], at mtus[o].  Datagram d of message
+ * o lands at outs[o] + d*pitch (device; pitch >= the largest mtu; 4-byte
+ * aligned slots take the fast stores), its length as vds_ec_dgram_layout says.
+ * All arrays HOST arrays; keys as above.  A lane reads its slice of the
+ * message once and writes only its datagram's own bytes.  Validation as above,
+ * and type >= 32, an mtu or route length vds_ec_dgram_layout rejects, a null
+ * output, pitch below an mtu or >= 2^32, index0[o] + its datagram count past
+ * 2^32 (the reference's "Overflow pipeline"), 2^31 datagrams or more:
+ * VDS_EC_EINVAL, before anything is enqueued.                                */
+int vds_ec_dgram_seal_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *msg_lens,
+                                   const uint8_t *types, const uint32_t *index0, const uint8_t *const *routes,
+                                   const uint32_t *route_lens, const uint32_t *session_of, const uint8_t *keys,
+                                   const uint32_t *mtus, uint32_t nsessions, uint8_t *const *outs, uint64_t pitch,
+                                   void *stream);
+/* Open `count` datagrams, one lane each: datagram j (lens[j] <= 65535 device
+ * bytes at dgrams[j]) is verified over lens[j] - 32 bytes against its last 32
+ * under session session_of[j]; verdicts[j] (device) = 0 verified, 1 invalid
+ * signature, 2 shorter than 33 bytes.  Its payload -- bytes [hdr_lens[j],
+ * lens[j] - 32) -- is copied to dsts[j] (device; dsts or dsts[j] may be NULL:
+ * verify only) ONLY when the datagram verified: unauthenticated bytes never
+ * reach a message buffer, and only the payload's own range is written.
+ * hdr_lens[j] > lens[j] - 32 (for lens[j] >= 33): VDS_EC_EINVAL; validation
+ * otherwise as above.                                                        */
+int vds_ec_dgram_open_batch_device(uint32_t count, const uint8_t *const *dgrams, const uint32_t *lens,
+                                   const uint32_t *hdr_lens, const uint32_t *session_of, const uint8_t *keys,
+                                   uint32_t nsessions, uint8_t *const *dsts, uint8_t *verdicts, void *stream);
+/* The seal from and to host memory on the calling thread's current device:
+ * messages, routes and keys in host memory; the datagrams of message o land
+ * back to back from slab + offsets[o] (all but its last are mtus[o] bytes, so
+ * datagram d starts at offsets[o] + d*mtus[o]), messages back to back;
+ * dgram_counts[o] and last_lens[o] as vds_ec_dgram_layout gives them.  The slab
+ * must hold the sum of the datagram lengths (VDS_EC_EINVAL otherwise).  Works
+ * through groups of at most 64 MiB of message bytes staged in pinned memory:
+ * one copy in, one launch, one copy out per group.  Validation as the device
+ * form's, every message before any transfer.                                 */
+int vds_ec_dgram_seal_host_batch(uint32_t count, const uint8_t *const *msgs, const uint64_t *msg_lens,
+                                 const uint8_t *types, const uint32_t *index0, const uint8_t *const *routes,
+                                 const uint32_t *route_lens, const uint32_t *session_of, const uint8_t *keys,
+                                 const uint32_t *mtus, uint32_t nsessions, uint8_t *slab, uint64_t slab_bytes,
+                                 uint64_t *offsets, uint32_t *dgram_counts, uint32_t *last_lens);
+/* A message found by vds_ec_dgram_open_host_batch.  status VDS_EC_OK: the route
+ * blob (route_len bytes: 0, 32 or 33 + 32 h) is at slab + route_off and the
+ * message (msg_len bytes) at slab + msg_off.  Any other status hands out no
+ * bytes (offsets and lengths zero): VDS_EC_EDGRAM_DATA where the reference
+ * answers "Invalid data" from authenticated headers, VDS_EC_EDGRAM_INCOMPLETE
+ * where a datagram is missing or one the message is made of did not verify.  */
+typedef struct vds_ec_dgram_message {
+  uint32_t session;
+  uint32_t index0; /* index of its first datagram */
+  uint32_t dgrams; /* datagrams it was planned from */
+  uint32_t type;
+  int32_t status;
+  uint32_t route_len;
+  uint64_t route_off;
+  uint64_t msg_off;
+  uint64_t msg_len;
+} vds_ec_dgram_message;
+/* Open the datagrams of a drained socket batch, in arrival order, each with its
+ * session (host memory).  Headers are parsed on the host to plan where every
+ * payload goes: per session the FIRST arrival of an index wins
+ * (process_datagram, :172-186); a first datagram starts a message, which takes
+ * the continuations at the following indices until the announced size is
+ * reached, with the reference's checks as written (:663-:726, the fixed
+ * constant of the ProxyData check at :687 included).  Then the datagrams are
+ * staged in groups of at most 64 MiB, opened in one launch per group, and the
+ * verdicts and assembled messages copied back.  verdicts[j] (host, count
+ * bytes): 0 / 1 / 2 as the device form, 3 = service datagram (first byte 6,
+ * MTUTest, or 7, Acknowledgment: unsigned, skipped).  messages (host, room for
+ * `count`) receives *nmessages records ordered by (session, index0).  A message
+ * is VDS_EC_OK only if EVERY datagram it is made of verified, its first
+ * included, so every header field that planned it is authenticated after the
+ * fact.  The slab needs no more than the sum of the datagram lengths
+ * (VDS_EC_EINVAL when the planned messages do not fit).  Validation as the
+ * device form's.                                                             */
+int vds_ec_dgram_open_host_batch(uint32_t count, const uint8_t *const *dgrams, const uint32_t *lens,
+                                 const uint32_t *session_of, const uint8_t *keys, uint32_t nsessions,
+                                 uint8_t *verdicts, uint8_t *slab, uint64_t slab_bytes,
+                                 vds_ec_dgram_message *messages, uint32_t *nmessages);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

@@ -23,6 +23,9 @@ EB64_LENGTH = -7
 EB64_PADDING = -8
 EB64_CHAR = -9
 ECORRUPT = -10
+EDGRAM_SIGNATURE = -11
+EDGRAM_DATA = -12
+EDGRAM_INCOMPLETE = -13
 
 F_NO_TRAILER = 0x1
 F_CELLS = 0x2
@@ -32,6 +35,16 @@ u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
 u64p = C.POINTER(C.c_uint64)
 vpp = C.POINTER(C.c_void_p)
+u32p = C.POINTER(C.c_uint32)
+
+
+class DgramMessage(C.Structure):
+    """vds_ec_dgram_message (include/vds_ec.h)."""
+    _fields_ = [("session", C.c_uint32), ("index0", C.c_uint32), ("dgrams", C.c_uint32), ("type", C.c_uint32),
+                ("status", C.c_int32), ("route_len", C.c_uint32), ("route_off", C.c_uint64),
+                ("msg_off", C.c_uint64), ("msg_len", C.c_uint64)]
+
+
 SIGNATURES = {
     "vds_ec_strerror": (C.c_char_p, [C.c_int]),
     "vds_ec_version": (C.c_int, []),
@@ -112,6 +125,19 @@ SIGNATURES = {
     "vds_ec_download16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, u16p, vpp, u64p, C.c_void_p, u16p,
                                                C.c_void_p, vpp, u64p, C.POINTER(C.c_int32), C.c_void_p,
                                                C.POINTER(C.c_uint32)]),
+    "vds_ec_hmac_sha256_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vds_ec_dgram_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, u32p, u32p, u32p]),
+    "vds_ec_write_number": (C.c_int, [C.c_uint64, C.c_void_p, u32p]),
+    "vds_ec_hmac_sha256_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, u32p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vds_ec_dgram_seal_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, u32p, vpp, u32p, u32p, C.c_void_p,
+                                                 u32p, C.c_uint32, vpp, C.c_uint64, C.c_void_p]),
+    "vds_ec_dgram_open_batch_device": (C.c_int, [C.c_uint32, vpp, u32p, u32p, u32p, C.c_void_p, C.c_uint32, vpp,
+                                                 C.c_void_p, C.c_void_p]),
+    "vds_ec_dgram_seal_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, u32p, vpp, u32p, u32p, C.c_void_p,
+                                               u32p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u32p, u32p]),
+    "vds_ec_dgram_open_host_batch": (C.c_int, [C.c_uint32, vpp, u32p, u32p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_uint64, C.POINTER(DgramMessage), u32p]),
     "vds_ec_base64_decoded_size": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "vds_ec_base64_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "vds_ec_base64_encode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

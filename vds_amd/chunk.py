@@ -35,6 +35,8 @@ __all__ = [
     "restore_host_split", "sha256_batch_device", "save_temp_batch_device", "save_temp_batch",
     "base64_decode_batch_device", "base64_encode_batch_device", "upload_batch",
     "base64_encode_gated_batch_device", "download_batch_device", "download_batch",
+    "hmac_sha256_host", "dgram_layout", "write_number", "hmac_sha256_batch_device", "dgram_seal_batch_device",
+    "dgram_open_batch_device", "dgram_seal_batch", "dgram_open_batch",
 ]
 
 
@@ -944,3 +946,181 @@ def host_register(arr) -> None:
 
 def host_unregister(arr) -> None:
     check(_lib.lib().vds_ec_host_unregister(_u8(arr).ctypes.data), "host_unregister")
+
+
+# ------------------------------------------------------- node-to-node transport
+def hmac_sha256_host(key, data) -> bytes:
+    """vds_ec_hmac_sha256_host: HMAC-SHA256 of one host message on the calling
+    thread (hmac::signature, kernel/vds_crypto/hash.cpp:218-260)."""
+    k, d = _u8(key), _u8(data)
+    out = np.empty(32, dtype=np.uint8)
+    check(_lib.lib().vds_ec_hmac_sha256_host(k.ctypes.data if k.size else None, k.size,
+                                             d.ctypes.data if d.size else None, d.size, out.ctypes.data),
+          "hmac_sha256_host")
+    return out.tobytes()
+
+
+def dgram_layout(mtu: int, route_len: int, msg_len: int) -> tuple:
+    """vds_ec_dgram_layout: (datagram count, message bytes in the first, length
+    of the last) as prepare_to_send cuts a message
+    (dht_datagram_protocol.cpp:335-541)."""
+    n, c0, last = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.lib().vds_ec_dgram_layout(mtu, route_len, msg_len, C.byref(n), C.byref(c0), C.byref(last)),
+          "dgram_layout")
+    return n.value, c0.value, last.value
+
+
+def write_number(value: int) -> bytes:
+    """vds_ec_write_number: binary_serializer::write_number
+    (binary_serialize.cpp:44-66)."""
+    out = np.empty(9, dtype=np.uint8)
+    n = C.c_uint32(0)
+    check(_lib.lib().vds_ec_write_number(value, out.ctypes.data, C.byref(n)), "write_number")
+    return out[:n.value].tobytes()
+
+
+def _u32(values) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(values, dtype=np.uint32).reshape(-1))
+
+
+def _keys(keys) -> np.ndarray:
+    """Session keys (a sequence of 32-byte keys, or their bytes back to back)."""
+    if isinstance(keys, (bytes, bytearray, memoryview, np.ndarray)):
+        return _u8(keys)
+    return _u8(b"".join(bytes(k) for k in keys))
+
+
+def hmac_sha256_batch_device(msgs, lens, session_of, keys, macs, expected=None, verdicts=None, stream=None) -> None:
+    """vds_ec_hmac_sha256_batch_device: HMAC-SHA256 of len(lens) device
+    messages in one launch -- message j is lens[j] bytes at the device pointer
+    msgs[j], under key session_of[j] of keys (host, 32 bytes each); MAC j goes
+    to macs + 32 j (device; None with expected: check only) and, with expected,
+    is compared into verdicts[j] (device; 0 equal, 1 different)."""
+    mp = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    so, ks = _u32(session_of), _keys(keys)
+    if not (mp.size == ln.size == so.size) or ks.size % 32:
+        raise VdsEcError(_lib.EINVAL, "hmac_sha256_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_hmac_sha256_batch_device(ln.size, mp.ctypes.data_as(_lib.vpp),
+                                                     ln.ctypes.data_as(_lib.u64p), so.ctypes.data_as(_lib.u32p),
+                                                     ks.ctypes.data if ks.size else None, ks.size // 32,
+                                                     _dev_ptr(macs), _dev_ptr(expected), _dev_ptr(verdicts),
+                                                     _stream_ptr(stream)), "hmac_sha256_batch_device")
+
+
+def dgram_seal_batch_device(msgs, msg_lens, types, index0, routes, route_lens, session_of, keys, mtus, outs,
+                            pitch: int, stream=None) -> None:
+    """vds_ec_dgram_seal_batch_device: message o (msg_lens[o] bytes at the
+    device pointer msgs[o]) cut into datagrams, each with its header and
+    HMAC-SHA256 under key session_of[o]; datagram d of message o lands at the
+    device pointer outs[o] + d * pitch, as long as dgram_layout says.  routes[o]
+    is the device pointer of its route blob (route_lens[o] bytes)."""
+    mp = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(msg_lens, dtype=np.uint64).reshape(-1))
+    ty = np.ascontiguousarray(np.asarray(types, dtype=np.uint8).reshape(-1))
+    i0, rl, so, mt = _u32(index0), _u32(route_lens), _u32(session_of), _u32(mtus)
+    rp = np.ascontiguousarray(np.asarray(routes, dtype=np.uint64).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    ks = _keys(keys)
+    if not (mp.size == ln.size == ty.size == i0.size == rl.size == so.size == mt.size == rp.size == op.size) \
+            or ks.size % 32:
+        raise VdsEcError(_lib.EINVAL, "dgram_seal_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_dgram_seal_batch_device(ln.size, mp.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p),
+                                                    ty.ctypes.data, i0.ctypes.data_as(_lib.u32p),
+                                                    rp.ctypes.data_as(_lib.vpp), rl.ctypes.data_as(_lib.u32p),
+                                                    so.ctypes.data_as(_lib.u32p), ks.ctypes.data if ks.size else None,
+                                                    mt.ctypes.data_as(_lib.u32p), ks.size // 32,
+                                                    op.ctypes.data_as(_lib.vpp), pitch, _stream_ptr(stream)),
+          "dgram_seal_batch_device")
+
+
+def dgram_open_batch_device(dgrams, lens, hdr_lens, session_of, keys, dsts, verdicts, stream=None) -> None:
+    """vds_ec_dgram_open_batch_device: datagram j (lens[j] bytes at the device
+    pointer dgrams[j]) verified under key session_of[j]; verdicts[j] (device) =
+    0 verified, 1 invalid signature, 2 shorter than 33 bytes; bytes
+    [hdr_lens[j], lens[j] - 32) copied to the device pointer dsts[j] (0: nowhere;
+    dsts None: verify only) only when the datagram verified."""
+    dp = np.ascontiguousarray(np.asarray(dgrams, dtype=np.uint64).reshape(-1))
+    ln, hl, so, ks = _u32(lens), _u32(hdr_lens), _u32(session_of), _keys(keys)
+    tp = None if dsts is None else np.ascontiguousarray(np.asarray(dsts, dtype=np.uint64).reshape(-1))
+    if not (dp.size == ln.size == hl.size == so.size) or (tp is not None and tp.size != dp.size) or ks.size % 32:
+        raise VdsEcError(_lib.EINVAL, "dgram_open_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_dgram_open_batch_device(ln.size, dp.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u32p),
+                                                    hl.ctypes.data_as(_lib.u32p), so.ctypes.data_as(_lib.u32p),
+                                                    ks.ctypes.data if ks.size else None, ks.size // 32,
+                                                    None if tp is None else tp.ctypes.data_as(_lib.vpp),
+                                                    _dev_ptr(verdicts), _stream_ptr(stream)),
+          "dgram_open_batch_device")
+
+
+def dgram_seal_batch(msgs: Sequence, types: Sequence[int], index0: Sequence[int], routes: Sequence,
+                     session_of: Sequence[int], keys, mtus: Sequence[int]) -> list:
+    """vds_ec_dgram_seal_host_batch: host messages (bytes) with their route
+    blobs (bytes, b"" = direct) sealed on the device.  Returns per message the
+    list of its datagrams (bytes)."""
+    count = len(msgs)
+    mb = [_u8(m) for m in msgs]
+    rb = [_u8(r) for r in routes]
+    ln = np.asarray([m.size for m in mb], dtype=np.uint64)
+    rl = _u32([r.size for r in rb])
+    ty = np.ascontiguousarray(np.asarray(types, dtype=np.uint8).reshape(-1))
+    i0, so, mt, ks = _u32(index0), _u32(session_of), _u32(mtus), _keys(keys)
+    if not (count == ty.size == i0.size == rl.size == so.size == mt.size) or ks.size % 32:
+        raise VdsEcError(_lib.EINVAL, "dgram_seal_batch: the arrays do not describe one batch")
+    need = 0
+    for o in range(count):
+        n, _, last = dgram_layout(int(mt[o]), int(rl[o]), int(ln[o]))
+        need += (n - 1) * int(mt[o]) + last
+    slab = np.empty(max(1, need), dtype=np.uint8)
+    offs = np.zeros(max(1, count), dtype=np.uint64)
+    cnts = np.zeros(max(1, count), dtype=np.uint32)
+    lasts = np.zeros(max(1, count), dtype=np.uint32)
+    mp = (C.c_void_p * max(1, count))(*[m.ctypes.data if m.size else None for m in mb])
+    rp = (C.c_void_p * max(1, count))(*[r.ctypes.data if r.size else None for r in rb])
+    check(_lib.lib().vds_ec_dgram_seal_host_batch(count, mp, ln.ctypes.data_as(_lib.u64p), ty.ctypes.data,
+                                                  i0.ctypes.data_as(_lib.u32p), rp, rl.ctypes.data_as(_lib.u32p),
+                                                  so.ctypes.data_as(_lib.u32p), ks.ctypes.data if ks.size else None,
+                                                  mt.ctypes.data_as(_lib.u32p), ks.size // 32, slab.ctypes.data, need,
+                                                  offs.ctypes.data_as(_lib.u64p), cnts.ctypes.data_as(_lib.u32p),
+                                                  lasts.ctypes.data_as(_lib.u32p)), "dgram_seal_host_batch")
+    out = []
+    for o in range(count):
+        at, m = int(offs[o]), int(mt[o])
+        ds = [slab[at + d * m:at + (d + 1) * m].tobytes() for d in range(int(cnts[o]) - 1)]
+        at += (int(cnts[o]) - 1) * m
+        ds.append(slab[at:at + int(lasts[o])].tobytes())
+        out.append(ds)
+    return out
+
+
+def dgram_open_batch(dgrams: Sequence, session_of: Sequence[int], keys) -> tuple:
+    """vds_ec_dgram_open_host_batch: the datagrams of a drained socket batch
+    (bytes, arrival order) with their sessions.  Returns (verdicts, messages):
+    verdicts[j] = 0 verified, 1 invalid signature, 2 shorter than 33 bytes, 3
+    service datagram skipped; messages = a list of dicts (session, index0,
+    dgrams, type, status, route, message) ordered by (session, index0), route
+    and message None unless status is 0."""
+    count = len(dgrams)
+    db = [_u8(d) for d in dgrams]
+    ln, so, ks = _u32([d.size for d in db]), _u32(session_of), _keys(keys)
+    if count != so.size or ks.size % 32:
+        raise VdsEcError(_lib.EINVAL, "dgram_open_batch: the arrays do not describe one batch")
+    cap = int(ln.sum()) if count else 0
+    slab = np.empty(max(1, cap), dtype=np.uint8)
+    vd = np.zeros(max(1, count), dtype=np.uint8)
+    msgs = (_lib.DgramMessage * max(1, count))()
+    nm = C.c_uint32(0)
+    dp = (C.c_void_p * max(1, count))(*[d.ctypes.data if d.size else None for d in db])
+    check(_lib.lib().vds_ec_dgram_open_host_batch(count, dp, ln.ctypes.data_as(_lib.u32p),
+                                                  so.ctypes.data_as(_lib.u32p), ks.ctypes.data if ks.size else None,
+                                                  ks.size // 32, vd.ctypes.data, slab.ctypes.data, cap, msgs,
+                                                  C.byref(nm)), "dgram_open_host_batch")
+    out = []
+    for i in range(nm.value):
+        m = msgs[i]
+        ok = m.status == 0
+        out.append({"session": m.session, "index0": m.index0, "dgrams": m.dgrams, "type": m.type,
+                    "status": m.status,
+                    "route": slab[m.route_off:m.route_off + m.route_len].tobytes() if ok else None,
+                    "message": slab[m.msg_off:m.msg_off + m.msg_len].tobytes() if ok else None})
+    return [int(v) for v in vd[:count]], out

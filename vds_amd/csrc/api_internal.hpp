@@ -17,6 +17,8 @@
 //   api_download_batch.cpp  the download loop in one call: the name check
 //                       (survivors or a witness), the batched restore and the
 //                       gated base64 encode (device and host);
+//   api_dgram_batch.cpp  the node-to-node datagram layer: batched HMAC-SHA256,
+//                       sealing and opening of datagrams (device and host);
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -236,6 +238,26 @@ int download_host_batch(uint32_t k, uint32_t count, const uint16_t *nodes, const
                         const uint64_t *chunk_sizes, const uint8_t *survivor_names, const uint16_t *witness_ids,
                         const uint8_t *witness_names, char *const *texts, uint64_t *text_lens, int32_t *statuses,
                         uint8_t *survivor_verdicts, uint32_t *failed);
+// the node-to-node datagram layer (api_dgram_batch.cpp, dgram.hip)
+int hmac_sha256_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
+                             const uint32_t *session_of, const uint8_t *keys, uint32_t nsessions, uint8_t *macs,
+                             const uint8_t *expected, uint8_t *verdicts, hipStream_t s);
+int dgram_seal_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *msg_lens,
+                            const uint8_t *types, const uint32_t *index0, const uint8_t *const *routes,
+                            const uint32_t *route_lens, const uint32_t *session_of, const uint8_t *keys,
+                            const uint32_t *mtus, uint32_t nsessions, uint8_t *const *outs, uint64_t pitch,
+                            hipStream_t s);
+int dgram_open_batch_device(uint32_t count, const uint8_t *const *dgrams, const uint32_t *lens,
+                            const uint32_t *hdr_lens, const uint32_t *session_of, const uint8_t *keys,
+                            uint32_t nsessions, uint8_t *const *dsts, uint8_t *verdicts, hipStream_t s);
+int dgram_seal_host_batch(uint32_t count, const uint8_t *const *msgs, const uint64_t *msg_lens, const uint8_t *types,
+                          const uint32_t *index0, const uint8_t *const *routes, const uint32_t *route_lens,
+                          const uint32_t *session_of, const uint8_t *keys, const uint32_t *mtus, uint32_t nsessions,
+                          uint8_t *slab, uint64_t slab_bytes, uint64_t *offsets, uint32_t *dgram_counts,
+                          uint32_t *last_lens);
+int dgram_open_host_batch(uint32_t count, const uint8_t *const *dgrams, const uint32_t *lens,
+                          const uint32_t *session_of, const uint8_t *keys, uint32_t nsessions, uint8_t *verdicts,
+                          uint8_t *slab, uint64_t slab_bytes, vds_ec_dgram_message *messages, uint32_t *nmessages);
 hipError_t param_acquire_n(int cnt, const size_t *bytes, ParamSlot **out);
 hipError_t param_commit(ParamSlot *sl, size_t bytes, hipStream_t s);
 hipError_t param_release(ParamSlot *sl, hipStream_t s);

@@ -181,6 +181,63 @@ struct B64EncGate {
   uint32_t reserved;
 };
 
+// Node-to-node datagrams (dgram.hip): HMAC-SHA256 under a session key, one
+// lane per message or datagram.  The key pads are hashed once per session ON
+// THE HOST (two compressions, sha256_host.cpp): keys[s] holds the SHA-256
+// states after the 64-byte block key ^ 0x36.. (inner) and key ^ 0x5c.. (outer),
+// so a lane of n bytes costs (n + 8) / 64 + 1 inner compressions and one outer.
+struct HmacKeyState {
+  uint32_t inner[8];
+  uint32_t outer[8];
+};
+// One lane of k_hmac_sha256_batch / k_dgram_open, in launch order (the host
+// orders the lanes by length; `index` is the caller's position).
+struct HmacLane {
+  uint64_t src;      // len bytes, any alignment (len == 0: never dereferenced)
+  uint64_t dst;      // open: where bytes [hdr_len, len - 32) go once verified (0: nowhere)
+  uint32_t len;
+  uint32_t hdr_len;  // open only; at most len - 32
+  uint32_t session;  // keys[session]
+  uint32_t index;    // MAC at macs + 32 index, expected + 32 index, verdict at verdicts + index
+};
+struct HmacBatchLaunch {
+  const HmacLane *lanes;
+  const HmacKeyState *keys;
+  uint32_t count;
+  uint64_t macs;      // 0: no MAC written (check only)
+  uint64_t expected;  // 0: nothing compared, no verdict written
+  uint64_t verdicts;  // 0 equal / 1 different
+};
+struct DgramOpenLaunch {
+  const HmacLane *lanes;
+  const HmacKeyState *keys;
+  uint32_t count;
+  uint64_t verdicts;  // 0 verified / 1 invalid signature / 2 shorter than 33 bytes
+};
+// One message of k_dgram_seal; its datagrams are lanes first .. first + its
+// datagram count - 1 (first ascending), datagram d at out + d * pitch.
+// wave_msg[w] is the message that owns lane 64 w (waves + 1 entries, the last
+// for lane 64 waves), so a lane finds its message between two entries.
+struct DgramSealMsg {
+  uint64_t msg;    // len bytes, any alignment
+  uint64_t route;  // route_len bytes, any alignment
+  uint64_t out;
+  uint32_t len;
+  uint32_t index0;
+  uint32_t route_len;
+  uint32_t mtu;
+  uint32_t pitch;
+  uint32_t session;
+  uint32_t first;
+  uint32_t type;
+};
+struct DgramSealLaunch {
+  const DgramSealMsg *msgs;
+  const HmacKeyState *keys;
+  const uint32_t *wave_msg;
+  uint32_t lanes;
+};
+
 // Bit-sliced runtime-coefficient restore over 512-stripe groups: the first
 // groups_per_obj groups of every object as one stream of 4-group tiles.
 struct FastRestoreArgs {
@@ -425,6 +482,17 @@ hipError_t launch_sha256(const uint8_t *base, uint64_t len, uint64_t stride, uin
 hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s);
 // The same, and every group's check (ShaBatchCheck) in the same launch.
 hipError_t launch_sha256_check_batch(const ShaBatchCheckLaunch &c, hipStream_t s);
+// HMAC-SHA256 of every lane's message; sealing and opening of datagrams (dgram.hip).
+hipError_t launch_hmac_sha256_batch(const HmacBatchLaunch &b, hipStream_t s);
+hipError_t launch_dgram_seal(const DgramSealLaunch &b, hipStream_t s);
+// lane_copy: each lane copies its own payload (the A/B arm), else the wave copies them one after the other
+hipError_t launch_dgram_open(const DgramOpenLaunch &b, hipStream_t s, bool lane_copy = false);
+// The SHA-256 compression of sha256_host.cpp over nblocks 64-byte blocks, and
+// HMAC-SHA256 on the calling thread: the states after the two key pad blocks
+// (any key length; a key longer than 64 bytes is hashed first), and a whole MAC.
+void sha256_host_blocks(uint32_t h[8], const uint8_t *p, size_t nblocks);
+void hmac_sha256_host_midstates(const uint8_t *key, size_t key_len, uint32_t inner[8], uint32_t outer[8]);
+void hmac_sha256_host(const uint8_t *key, size_t key_len, const uint8_t *data, uint64_t len, uint8_t mac[32]);
 // base64 -> bytes of msgs[0..count) (device table), every status written (base64.hip).
 hipError_t launch_b64_decode_batch(const B64DecMsg *msgs, uint32_t count, hipStream_t s);
 // bytes -> base64 over tiles[0..ntiles) of msgs (device tables).

@@ -32,6 +32,9 @@
 #include "vds_ec.h"
 
 namespace vds_ec {
+void sha256_host_blocks(uint32_t h[8], const uint8_t *p, size_t nblocks);
+void hmac_sha256_host_midstates(const uint8_t *key, size_t key_len, uint32_t inner[8], uint32_t outer[8]);
+void hmac_sha256_host(const uint8_t *key, size_t key_len, const uint8_t *data, uint64_t len, uint8_t mac[32]);
 namespace {
 
 constexpr uint32_t kK[64] = {
@@ -137,9 +140,9 @@ BlocksFn blocks_fn() {
 
 }  // namespace
 
-void sha256_host(const uint8_t *data, uint64_t len, uint8_t out[32]) {
-  uint32_t h[8];
-  std::memcpy(h, kH0, sizeof h);
+// Finish a chain whose state h has already taken `before` bytes (a multiple of
+// 64): data, the 0x80, zeros and the 64-bit big-endian bit length.
+static void sha256_finish(uint32_t h[8], uint64_t before, const uint8_t *data, uint64_t len, uint8_t out[32]) {
   const BlocksFn f = blocks_fn();
   const uint64_t full = len / 64;
   if (full) f(h, data, full);
@@ -148,7 +151,7 @@ void sha256_host(const uint8_t *data, uint64_t len, uint8_t out[32]) {
   if (rem) std::memcpy(tail, data + 64 * full, rem);
   tail[rem] = 0x80;
   const size_t tb = rem + 9 <= 64 ? 64 : 128;
-  const uint64_t bits = len * 8;
+  const uint64_t bits = (before + len) * 8;
   for (int i = 0; i < 8; ++i) tail[tb - 1 - i] = (uint8_t)(bits >> (8 * i));
   f(h, tail, tb / 64);
   for (int i = 0; i < 8; ++i) {
@@ -159,10 +162,50 @@ void sha256_host(const uint8_t *data, uint64_t len, uint8_t out[32]) {
   }
 }
 
+void sha256_host(const uint8_t *data, uint64_t len, uint8_t out[32]) {
+  uint32_t h[8];
+  std::memcpy(h, kH0, sizeof h);
+  sha256_finish(h, 0, data, len, out);
+}
+
+void sha256_host_blocks(uint32_t h[8], const uint8_t *p, size_t nblocks) { blocks_fn()(h, p, nblocks); }
+
+// HMAC (RFC 2104) as OpenSSL's HMAC, which hmac::signature / hmac::verify call
+// (kernel/vds_crypto/hash.cpp:218-260): K' = the key zero-padded to 64 bytes
+// (SHA-256 of it first when it is longer), MAC = H(K' ^ 5c.. || H(K' ^ 36.. || data)).
+void hmac_sha256_host_midstates(const uint8_t *key, size_t key_len, uint32_t inner[8], uint32_t outer[8]) {
+  uint8_t k0[64] = {}, pad[64];
+  if (key_len > 64)
+    sha256_host(key, key_len, k0);
+  else if (key_len)
+    std::memcpy(k0, key, key_len);
+  std::memcpy(inner, kH0, sizeof kH0);
+  std::memcpy(outer, kH0, sizeof kH0);
+  for (int i = 0; i < 64; ++i) pad[i] = k0[i] ^ 0x36;
+  sha256_host_blocks(inner, pad, 1);
+  for (int i = 0; i < 64; ++i) pad[i] = k0[i] ^ 0x5c;
+  sha256_host_blocks(outer, pad, 1);
+}
+
+void hmac_sha256_host(const uint8_t *key, size_t key_len, const uint8_t *data, uint64_t len, uint8_t mac[32]) {
+  uint32_t inner[8], outer[8];
+  hmac_sha256_host_midstates(key, key_len, inner, outer);
+  uint8_t digest[32];
+  sha256_finish(inner, 64, data, len, digest);
+  sha256_finish(outer, 64, digest, 32, mac);
+}
+
 }  // namespace vds_ec
 
 extern "C" int vds_ec_sha256_host(const uint8_t *data, uint64_t len, uint8_t *digest) {
   if (!digest || (len && !data)) return VDS_EC_EINVAL;
   vds_ec::sha256_host(data, len, digest);
+  return VDS_EC_OK;
+}
+
+extern "C" int vds_ec_hmac_sha256_host(const uint8_t *key, uint64_t key_len, const uint8_t *data, uint64_t len,
+                                       uint8_t *mac) {
+  if (!mac || (len && !data) || (key_len && !key)) return VDS_EC_EINVAL;
+  vds_ec::hmac_sha256_host(key, (size_t)key_len, data, len, mac);
   return VDS_EC_OK;
 }

@@ -1015,6 +1015,9 @@ const char *vds_ec_strerror(int status) {
     case VDS_EC_EB64_PADDING: return "Invalid Padding in Base 64!";
     case VDS_EC_EB64_CHAR: return "Non-Valid Character in Base 64!";
     case VDS_EC_ECORRUPT: return "Data is corrupted";
+    case VDS_EC_EDGRAM_SIGNATURE: return "Invalid signature";
+    case VDS_EC_EDGRAM_DATA: return "Invalid data";
+    case VDS_EC_EDGRAM_INCOMPLETE: return "message incomplete: a datagram is missing or did not verify";
     default: return "unknown vds_ec status";
   }
 }

@@ -163,4 +163,52 @@ int vds_ec_upload_response_json(int id, const uint8_t *replica_digests, uint32_t
   return copy_out(s, out, cap, out_len);
 }
 
+// How prepare_to_send cuts a message (impl/dht_datagram_protocol.cpp:335-541):
+// total = 1 + 4 + route + message + 32; below the mtu it is one datagram, else
+// the first carries BE32(size) too and is exactly mtu bytes, and each
+// continuation carries up to mtu - 37 bytes.
+int vds_ec_dgram_layout(uint32_t mtu, uint32_t route_len, uint64_t msg_len, uint32_t *count, uint32_t *first_payload,
+                        uint32_t *last_len) {
+  if (mtu < 508 || mtu > 65535 || msg_len > 0xFFFFFFFFull) return VDS_EC_EINVAL;
+  const bool proxy = route_len >= 33 && (route_len - 33) % 32 == 0 && (route_len - 33) / 32 < 256;
+  const bool route_ok = route_len == 0 || route_len == 32 || proxy;
+  if (!route_ok || 41ull + route_len >= mtu) return VDS_EC_EINVAL;
+  uint32_t n = 1, c0 = (uint32_t)msg_len, last = 0;
+  if (37ull + route_len + msg_len < mtu) {
+    last = 37 + route_len + (uint32_t)msg_len;
+  } else {
+    c0 = mtu - (41 + route_len);
+    const uint64_t per = mtu - 37, rest = msg_len - c0;
+    n = 1 + (uint32_t)((rest + per - 1) / per);
+    last = 37 + (uint32_t)(rest - (uint64_t)(n - 2) * per);
+  }
+  if (count) *count = n;
+  if (first_payload) *first_payload = c0;
+  if (last_len) *last_len = last;
+  return VDS_EC_OK;
+}
+
+// binary_serializer::write_number (binary_serialize.cpp:44-66): one byte below
+// 128, else 0x80 | n and the n big-endian bytes of value - 128.
+int vds_ec_write_number(uint64_t value, uint8_t *out, uint32_t *len) {
+  if (!out || !len) return VDS_EC_EINVAL;
+  if (value < 128) {
+    out[0] = (uint8_t)value;
+    *len = 1;
+    return VDS_EC_OK;
+  }
+  value -= 128;
+  uint8_t data[8];
+  int index = 0;
+  do {
+    data[index++] = (uint8_t)(value & 0xFF);
+    value >>= 8;
+  } while (value != 0);
+  uint32_t at = 0;
+  out[at++] = (uint8_t)(0x80 | index);
+  while (index > 0) out[at++] = data[--index];
+  *len = at;
+  return VDS_EC_OK;
+}
+
 }  // extern "C"
