@@ -61,8 +61,12 @@ def test_hmac_host_rfc4231(case):
 
 def test_layout_against_restatement():
     from vds_amd import chunk
-    for mtu in (508, 509, 1400, 65535):
-        for r in (0, 32, 97):
+    # (with the shapes of tests/test_dgram_edges_gpu.py: proxied routes of 4 to
+    # 255 hops, r = 33 + 32 hops, wherever 41 + r fits the mtu, and mtu 9000)
+    for mtu in (508, 509, 1400, 9000, 65535):
+        for r in (0, 32, 33, 97, 161, 193, 449, 673, 1313, 8193):
+            if 41 + r >= mtu:
+                continue
             c0 = mtu - (41 + r)
             per = mtu - 37
             ms = {0, 1, c0 - 1, c0, c0 + 3, c0 + 4, c0 + 5, c0 + per - 1, c0 + per, c0 + per + 1, c0 + 2 * per,
