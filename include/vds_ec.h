@@ -51,6 +51,11 @@ extern "C" {
 #define VDS_EC_EDGRAM_SIGNATURE (-11)  /* "Invalid signature"                   */
 #define VDS_EC_EDGRAM_DATA (-12)       /* "Invalid data"                        */
 #define VDS_EC_EDGRAM_INCOMPLETE (-13) /* a message whose datagrams are not all present and verified */
+/* websocket frames (vds_ec_ws_*) */
+#define VDS_EC_EWS_SHORT (-14) /* the frame's header (or, in a batch, the frame) is not all there yet */
+#define VDS_EC_EWS_FRAME (-15) /* "Not implemented" (an opcode other than text, binary and ping)   */
+#define VDS_EC_EWS_FORM (-16)  /* not the fast form of "upload": the caller's own parser decides     */
+#define VDS_EC_EWS_PING (-17)  /* a ping met in a batch: no device work, the caller sends its pong   */
 
 /* ----------------------------------------------------------------- flags */
 /* write_padding = false in chunk_generator::write (chunk.h:79,273-278):
@@ -754,6 +759,161 @@ int vds_ec_dgram_open_host_batch(uint32_t count, const uint8_t *const *dgrams, c
                                  const uint32_t *session_of, const uint8_t *keys, uint32_t nsessions,
                                  uint8_t *verdicts, uint8_t *slab, uint64_t slab_bytes,
                                  vds_ec_dgram_message *messages, uint32_t *nmessages);
+
+/* ------------------------------------------------------- websocket frames
+ * What the server holds after a socket read is a websocket FRAME
+ * (kernel/vds_http/websocket.cpp:45-201): a 2-, 4- or 10-byte header, a 4-byte
+ * mask when the mask bit is set, and the payload XOR-masked byte by byte --
+ * for "upload" the JSON text the web client's JSON.stringify produces,
+ * {"id":5,"invoke":"upload","params":["<base64>"]} (web/src/store/vds_ws.js).
+ * These calls take the frame and the upload / download envelope, and nothing
+ * else of vds_http: no continuation frames (the reference implements none: one
+ * frame is one message), no close, no pong, no handshake, no other method.
+ *
+ * vds_ec_ws_frame_parse: the header rules of websocket.cpp:54-109 as host
+ * arithmetic (no GPU).  FIN and RSV1-3 are reported and not acted on, as
+ * there.  header_len is 2 / 4 / 10 plus 4 with a mask; payload_len the 7-, 16-
+ * or 64-bit big-endian length.  Returns VDS_EC_OK for opcodes 1 (text), 2
+ * (binary) and 9 (ping: the caller sends its own pong), VDS_EC_EWS_FRAME for
+ * every other opcode (the reference's "Not implemented", :123-144; the fields
+ * are filled in all the same), VDS_EC_EWS_SHORT when len does not hold the
+ * whole header: then only `need` is meaningful, the number of bytes the call
+ * has to see to get further (2, then header_len).  (The reference waits for a
+ * third byte before it looks at the first two; a frame of two bytes in all --
+ * unmasked, empty -- is whole here.)  buf NULL with len > 0, frame NULL:
+ * VDS_EC_EINVAL.                                                             */
+typedef struct vds_ec_ws_frame {
+  uint8_t fin, rsv1, rsv2, rsv3;
+  uint8_t opcode;
+  uint8_t masked;
+  uint8_t mask[4]; /* zero when not masked */
+  uint32_t header_len;
+  uint32_t need;
+  uint64_t payload_len;
+} vds_ec_ws_frame;
+int vds_ec_ws_frame_parse(const uint8_t *buf, size_t len, vds_ec_ws_frame *frame);
+/* websocket_output::start (websocket.cpp:220-257): 0x81 (text) or 0x82
+ * (binary), then the length in its 7-bit form below 126, its 16-bit form up to
+ * 0xFFFF, else its 64-bit form; never masked.  out receives *len = 2, 4 or 10
+ * bytes.                                                                     */
+int vds_ec_ws_frame_header(uint64_t payload_len, int binary, uint8_t out[10], uint32_t *len);
+/* Recognise the FAST FORM of an "upload" request in a payload of len bytes,
+ * masked with mask[j & 3] at byte j (mask NULL: not masked): exactly
+ *   {"id":<int>,"invoke":"upload","params":["<body>"]}
+ * with <int> 0 or a decimal without leading zeros of at most 2^31 - 1 -- the
+ * text JSON.stringify makes of the web client's request.  *id, the body's
+ * offset and length in the payload, and *decoded_size =
+ * vds_ec_base64_decoded_size of the body (0 when its length is no multiple of
+ * 4) are returned.  At most the first 48 and the last 5 bytes of the payload
+ * are unmasked and read -- the envelope and the body's last two characters --:
+ * the body is never walked.  Anything else -- another key order, whitespace,
+ * another method, an id outside the form, a missing end -- is
+ * VDS_EC_EWS_FORM: "not the fast form, give it to your own parser".
+ * The rule this function and the masked decode keep TOGETHER: a message that
+ * comes out VDS_EC_OK of both has exactly the id, body and bytes the
+ * reference's json_parser and base64::to_bytes would have produced; any other
+ * status decides nothing and the caller may take its slow path.  A '"' or '\'
+ * inside the body is not looked for here: it is outside the alphabet, so the
+ * decode answers VDS_EC_EB64_CHAR (the reference would have ended the string
+ * there, and may even have succeeded: ["QUJD","x"]).  One exception is known
+ * and open: the decode, as base64::to_bytes, stops at the first '=', so a '"'
+ * BEHIND an early '=' in a body whose last two characters hold a '=' again
+ * (QQ=="],"x":["QQ==) is not seen and the message comes out VDS_EC_OK.  No
+ * JSON.stringify of a base64 string produces such a body.      */
+int vds_ec_ws_upload_request(const uint8_t *payload, uint64_t len, const uint8_t *mask, int32_t *id,
+                             uint64_t *body_off, uint64_t *body_len, uint64_t *decoded_size);
+/* The answer frames' arithmetic.  Upload: *frame_len = *header_len + the length
+ * of vds_ec_upload_response_json(id, n names, replica_size).  Download: the
+ * answer {"id":"<id>","result":"<text>"} (websocket_api.cpp:30-49, :772-782)
+ * of an object of E bytes: 21 + digits + (E + 2) / 3 * 4 bytes behind the
+ * header, the text at frame + *text_off.  The id is printed as
+ * vds_ec_upload_response_json prints it (a negative one as its 64-bit
+ * two's complement).  Any output may be NULL.                                */
+int vds_ec_ws_upload_answer_size(int id, uint32_t n, uint32_t replica_size, uint64_t *frame_len,
+                                 uint32_t *header_len);
+int vds_ec_ws_download_answer_layout(int id, uint64_t object_size, uint64_t *frame_len, uint32_t *header_len,
+                                     uint64_t *text_off);
+/* What process_message answers when a method fails (websocket_api.cpp:97-104):
+ * the frame header, then {"id":"<id>","error":"<vds_ec_strerror(status)>"} with
+ * the message escaped as json_writer.cpp:205-240 escapes.  out == NULL queries
+ * the length; cap below it: VDS_EC_EINVAL.  No NUL is written.               */
+int vds_ec_ws_error_answer(int id, int status, uint8_t *out, size_t cap, size_t *out_len);
+/* vds_ec_base64_decode_batch_device for texts still under their websocket
+ * mask: masks (HOST, 4 bytes a text) -- character j of text o is
+ * texts[o][j] ^ masks[4*o + (j & 3)], so the caller passes the frame's mask
+ * rotated by (body_off & 3).  Everything the kernel looks at is unmasked
+ * first: the characters a lane classifies, the two of the declared-size check,
+ * the character of the first event and the three the accumulator is rebuilt
+ * from.  Same kernel (a template instance), same statuses, same words read,
+ * same bytes written; a mask of zero gives the unmasked call's bytes and
+ * statuses.  masks NULL with count > 0: VDS_EC_EINVAL.                        */
+int vds_ec_base64_decode_masked_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
+                                             const uint8_t *masks, uint8_t *const *outs, const uint64_t *out_sizes,
+                                             int32_t *statuses, void *stream);
+/* The "upload" answers of a batch as FRAMES, written on the device where the
+ * names were made: frame o -- vds_ec_ws_frame_header, then the bytes of
+ * vds_ec_upload_response_json(ids[o], n names at replica_digests + 32*o*n, the
+ * body hash at data_digests + 32*o, replica_sizes[o]) -- at outs[o] (device,
+ * any alignment, vds_ec_ws_upload_answer_size bytes).  ids, replica_sizes,
+ * outs: HOST arrays; the digests device memory, any alignment, as
+ * vds_ec_save_temp16_batch_device leaves them.  Every name is 44 characters, so
+ * the layout is fixed but for the digits of the id and the replica size, which
+ * the host puts into the descriptor: one wave a message, a lane encodes one
+ * digest and waits for no other.  Only the frames' own bytes are written
+ * (dwords where aligned) and only the aligned words holding a digest byte are
+ * read.  The descriptors ride the pinned parameter ring.  Null arrays with
+ * count > 0, null replica_digests with n > 0, a null outs[o], n > 65536,
+ * count >= 2^30: VDS_EC_EINVAL, before the device is looked for; count == 0 is
+ * VDS_EC_OK.  Nothing synchronises.                                          */
+int vds_ec_ws_upload_answer_batch_device(uint32_t count, const int32_t *ids, uint32_t n,
+                                         const uint8_t *replica_digests, const uint8_t *data_digests,
+                                         const uint32_t *replica_sizes, uint8_t *const *outs, void *stream);
+/* vds_ec_upload16_host_batch fed with FRAMES and answering in frames: frame o
+ * is frame_lens[o] host bytes at frames[o] (one frame an entry; bytes behind
+ * it are ignored).  Per frame the header is parsed and the request recognised;
+ * a frame that is not all there (VDS_EC_EWS_SHORT), of another opcode
+ * (VDS_EC_EWS_FRAME), a ping (VDS_EC_EWS_PING) or not the fast form
+ * (VDS_EC_EWS_FORM) gets that status, no device work, no answer
+ * (answer_lens[o] = 0) and none of its outputs written.  The others' BODIES
+ * are gathered at 16-byte aligned offsets of pinned staging (the decode's fast
+ * load path), still masked; one copy in; the masked decode,
+ * vds_ec_save_temp16_batch_device and the answer launch into a device slab;
+ * one copy back of replicas, names, body hashes, statuses and answer frames.
+ * The host reads a payload only in memcpy and the at most 53 bytes of
+ * vds_ec_ws_upload_request.  statuses[o] (host, required) is then the body's
+ * vds_ec_base64_decode status; with a non-zero one none of the message's
+ * outputs is written and its answer is vds_ec_ws_error_answer(id, status).
+ * Answers land back to back in `answers` (host, answers_bytes): message o owns
+ * a slot at answer_offs[o] of max(its upload answer, its error answer for
+ * VDS_EC_EB64_CHAR, the longest) bytes, of which answer_lens[o] are written; a
+ * slab too small for the slots: VDS_EC_EINVAL.  *failed counts the frames
+ * whose status is not VDS_EC_OK.  replica_sizes, data_digests and failed may
+ * be NULL.  A replica buffer holds vds_ec_replica_size(2, k, S, 0) bytes for
+ * the body's decoded size S; payload_len / 4 * 3 is a bound on S that the
+ * frame header gives.  Groups of at most 64 MiB of bodies, one device, validation as
+ * vds_ec_upload16_host_batch's, every frame before any transfer.             */
+int vds_ec_ws_upload16_host_batch(uint16_t k, uint32_t n, uint32_t count, const uint8_t *const *frames,
+                                  const uint64_t *frame_lens, uint8_t *const *outs, uint8_t *replica_digests,
+                                  uint8_t *data_digests, uint32_t *replica_sizes, uint8_t *answers,
+                                  uint64_t answers_bytes, uint64_t *answer_offs, uint64_t *answer_lens,
+                                  int32_t *statuses, uint32_t *failed);
+/* vds_ec_download16_host_batch answering in FRAMES: ids (host, count) and a
+ * caller slab.  Object o owns a slot at frame_offs[o] of max(its answer frame
+ * as vds_ec_ws_download_answer_layout gives it, its error answer for
+ * VDS_EC_ERESTORE) bytes, slots back to back; an object whose first trailer
+ * has no answer owns the error answer's bytes only.  A passing object's slot
+ * receives header + {"id":"N","result":" + the text + "} -- the text copied
+ * once, from the staging straight to its place in the frame --, a failing one
+ * (VDS_EC_ECORRUPT, VDS_EC_ERESTORE) its vds_ec_ws_error_answer and never a
+ * character of text; frame_lens[o] is what was written.  statuses,
+ * survivor_verdicts, failed, modes and validation as there; a slab too small
+ * for the slots: VDS_EC_EINVAL.                                              */
+int vds_ec_ws_download16_host_batch(uint16_t k, uint32_t count, const int32_t *ids, const uint16_t *nodes,
+                                    const uint8_t *const *chunks, const uint64_t *chunk_sizes,
+                                    const uint8_t *survivor_names, const uint16_t *witness_ids,
+                                    const uint8_t *witness_names, uint8_t *slab, uint64_t slab_bytes,
+                                    uint64_t *frame_offs, uint64_t *frame_lens, int32_t *statuses,
+                                    uint8_t *survivor_verdicts, uint32_t *failed);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

@@ -26,6 +26,10 @@ ECORRUPT = -10
 EDGRAM_SIGNATURE = -11
 EDGRAM_DATA = -12
 EDGRAM_INCOMPLETE = -13
+EWS_SHORT = -14
+EWS_FRAME = -15
+EWS_FORM = -16
+EWS_PING = -17
 
 F_NO_TRAILER = 0x1
 F_CELLS = 0x2
@@ -44,6 +48,15 @@ class DgramMessage(C.Structure):
                 ("status", C.c_int32), ("route_len", C.c_uint32), ("route_off", C.c_uint64),
                 ("msg_off", C.c_uint64), ("msg_len", C.c_uint64)]
 
+
+class WsFrame(C.Structure):
+    """vds_ec_ws_frame (include/vds_ec.h)."""
+    _fields_ = [("fin", C.c_uint8), ("rsv1", C.c_uint8), ("rsv2", C.c_uint8), ("rsv3", C.c_uint8),
+                ("opcode", C.c_uint8), ("masked", C.c_uint8), ("mask", C.c_uint8 * 4), ("header_len", C.c_uint32),
+                ("need", C.c_uint32), ("payload_len", C.c_uint64)]
+
+
+i32p = C.POINTER(C.c_int32)
 
 SIGNATURES = {
     "vds_ec_strerror": (C.c_char_p, [C.c_int]),
@@ -138,6 +151,21 @@ SIGNATURES = {
                                                u32p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u32p, u32p]),
     "vds_ec_dgram_open_host_batch": (C.c_int, [C.c_uint32, vpp, u32p, u32p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_uint64, C.POINTER(DgramMessage), u32p]),
+    "vds_ec_ws_frame_parse": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(WsFrame)]),
+    "vds_ec_ws_frame_header": (C.c_int, [C.c_uint64, C.c_int, C.c_void_p, u32p]),
+    "vds_ec_ws_upload_request": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, i32p, u64p, u64p, u64p]),
+    "vds_ec_ws_upload_answer_size": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, u64p, u32p]),
+    "vds_ec_ws_download_answer_layout": (C.c_int, [C.c_int, C.c_uint64, u64p, u32p, u64p]),
+    "vds_ec_ws_error_answer": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vds_ec_base64_decode_masked_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, vpp, u64p, C.c_void_p,
+                                                           C.c_void_p]),
+    "vds_ec_ws_upload_answer_batch_device": (C.c_int, [C.c_uint32, i32p, C.c_uint32, C.c_void_p, C.c_void_p, u32p,
+                                                       vpp, C.c_void_p]),
+    "vds_ec_ws_upload16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, C.c_uint32, vpp, u64p, vpp, C.c_void_p,
+                                                C.c_void_p, u32p, C.c_void_p, C.c_uint64, u64p, u64p, i32p, u32p]),
+    "vds_ec_ws_download16_host_batch": (C.c_int, [C.c_uint16, C.c_uint32, i32p, u16p, vpp, u64p, C.c_void_p, u16p,
+                                                  C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p, i32p, C.c_void_p,
+                                                  u32p]),
     "vds_ec_base64_decoded_size": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "vds_ec_base64_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "vds_ec_base64_encode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -32,7 +32,7 @@ SOURCES = ["ec_encode_16_20.hip", "ec_encode_32_40.hip", "ec_encode_32_64.hip", 
            "ec_encode_batch_32_40.hip", "ec_encode_batch_16_20.hip", "ec_restore_syn_32a.hip",
            "ec_restore_syn_32b.hip", "ec_restore_syn_16.hip", "ec_encode.hip", "ec_restore_syn.hip", "ec_generic.hip",
            "ec_restore_bs.hip", "sha256.hip", "dgram.hip", "base64.hip", "vds_ec_api.cpp", "api_batch.cpp",
-           "api_encode_batch.cpp", "api_save_temp_batch.cpp", "api_upload_batch.cpp", "api_download_batch.cpp", "api_dgram_batch.cpp",
+           "api_encode_batch.cpp", "api_save_temp_batch.cpp", "api_upload_batch.cpp", "api_ws_batch.cpp", "api_download_batch.cpp", "api_dgram_batch.cpp",
            "api_host_batch.cpp", "api_param_ring.cpp", "vds_ec_wire.cpp", "vds_ec_jit.cpp", "sha256_host.cpp"]
 HOST_ONLY = {"sha256_host.cpp"}
 HEADERS = ["bitslice.hpp", "gf_common.hpp", "ec_internal.hpp", "ec_device.hpp", "restore_syn.hpp", "xorprog.hpp",

@@ -37,6 +37,9 @@ __all__ = [
     "base64_encode_gated_batch_device", "download_batch_device", "download_batch",
     "hmac_sha256_host", "dgram_layout", "write_number", "hmac_sha256_batch_device", "dgram_seal_batch_device",
     "dgram_open_batch_device", "dgram_seal_batch", "dgram_open_batch",
+    "ws_frame_parse", "ws_frame_header", "ws_upload_request", "ws_upload_answer_size", "ws_download_answer_layout",
+    "ws_error_answer", "base64_decode_masked_batch_device", "ws_upload_answer_batch_device", "ws_upload_batch",
+    "ws_download_batch",
 ]
 
 
@@ -1124,3 +1127,183 @@ def dgram_open_batch(dgrams: Sequence, session_of: Sequence[int], keys) -> tuple
                     "route": slab[m.route_off:m.route_off + m.route_len].tobytes() if ok else None,
                     "message": slab[m.msg_off:m.msg_off + m.msg_len].tobytes() if ok else None})
     return [int(v) for v in vd[:count]], out
+
+
+# ------------------------------------------------------------ websocket frames
+def ws_frame_parse(buf) -> tuple:
+    """vds_ec_ws_frame_parse: (status, frame) of the frame header at the start
+    of buf; status OK (text, binary, ping), EWS_FRAME (another opcode) or
+    EWS_SHORT (frame["need"] bytes are needed).  frame holds fin, rsv1-3,
+    opcode, masked, mask (bytes), header_len, need, payload_len."""
+    b = bytes(buf)
+    f = _lib.WsFrame()
+    rc = _lib.lib().vds_ec_ws_frame_parse(b, len(b), C.byref(f))
+    if rc == _lib.EINVAL:
+        raise VdsEcError(rc, "ws_frame_parse")
+    d = {name: getattr(f, name) for name, _ in _lib.WsFrame._fields_ if name != "mask"}
+    d["mask"] = bytes(f.mask)
+    return rc, d
+
+
+def ws_frame_header(payload_len: int, binary: bool = False) -> bytes:
+    """vds_ec_ws_frame_header: the 2, 4 or 10 header bytes of an unmasked frame."""
+    out = (C.c_uint8 * 10)()
+    n = C.c_uint32(0)
+    check(_lib.lib().vds_ec_ws_frame_header(payload_len, int(binary), out, C.byref(n)), "ws_frame_header")
+    return bytes(out[:n.value])
+
+
+def ws_upload_request(payload, mask: bytes | None = None) -> tuple:
+    """vds_ec_ws_upload_request: (status, id, body_off, body_len, decoded_size)
+    of a payload still under `mask` (None: not masked); status OK or EWS_FORM."""
+    b = bytes(payload)
+    rid, off, ln, size = C.c_int32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    mk = bytes(mask) if mask is not None else None
+    rc = _lib.lib().vds_ec_ws_upload_request(b, len(b), mk, C.byref(rid), C.byref(off), C.byref(ln), C.byref(size))
+    if rc == _lib.EINVAL:
+        raise VdsEcError(rc, "ws_upload_request")
+    return rc, rid.value, off.value, ln.value, size.value
+
+
+def ws_upload_answer_size(req_id: int, n: int, replica_size_: int) -> tuple:
+    """vds_ec_ws_upload_answer_size: (frame_len, header_len)."""
+    fl, hl = C.c_uint64(0), C.c_uint32(0)
+    check(_lib.lib().vds_ec_ws_upload_answer_size(req_id, n, replica_size_, C.byref(fl), C.byref(hl)))
+    return fl.value, hl.value
+
+
+def ws_download_answer_layout(req_id: int, object_size: int) -> tuple:
+    """vds_ec_ws_download_answer_layout: (frame_len, header_len, text_off)."""
+    fl, hl, to = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+    check(_lib.lib().vds_ec_ws_download_answer_layout(req_id, object_size, C.byref(fl), C.byref(hl), C.byref(to)))
+    return fl.value, hl.value, to.value
+
+
+def ws_error_answer(req_id: int, status: int) -> bytes:
+    """vds_ec_ws_error_answer: the frame {"id":"..","error":".."} behind its header."""
+    ln = C.c_size_t(0)
+    check(_lib.lib().vds_ec_ws_error_answer(req_id, status, None, 0, C.byref(ln)))
+    out = C.create_string_buffer(max(1, ln.value))
+    check(_lib.lib().vds_ec_ws_error_answer(req_id, status, out, ln.value, C.byref(ln)))
+    return out.raw[:ln.value]
+
+
+def base64_decode_masked_batch_device(texts, text_lens, masks, outs, out_sizes, statuses, stream=None) -> None:
+    """vds_ec_base64_decode_masked_batch_device: base64_decode_batch_device for
+    texts still under their websocket masks -- masks holds 4 bytes a text, and
+    character j of text o is texts[o][j] ^ masks[o][j & 3]."""
+    tp = np.ascontiguousarray(np.asarray(texts, dtype=np.uint64).reshape(-1))
+    tl = np.ascontiguousarray(np.asarray(text_lens, dtype=np.uint64).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    os_ = np.ascontiguousarray(np.asarray(out_sizes, dtype=np.uint64).reshape(-1))
+    if isinstance(masks, (bytes, bytearray)):
+        masks = np.frombuffer(bytes(masks), dtype=np.uint8)
+    mk = np.ascontiguousarray(np.asarray(masks, dtype=np.uint8).reshape(-1))
+    if not (tp.size == tl.size == op.size == os_.size and mk.size == 4 * tl.size):
+        raise VdsEcError(_lib.EINVAL, "base64_decode_masked_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_base64_decode_masked_batch_device(
+        tl.size, tp.ctypes.data_as(_lib.vpp), tl.ctypes.data_as(_lib.u64p), mk.ctypes.data,
+        op.ctypes.data_as(_lib.vpp), os_.ctypes.data_as(_lib.u64p), _dev_ptr(statuses), _stream_ptr(stream)),
+        "base64_decode_masked_batch_device")
+
+
+def ws_upload_answer_batch_device(req_ids, n: int, replica_digests, data_digests, replica_sizes, outs,
+                                  stream=None) -> None:
+    """vds_ec_ws_upload_answer_batch_device: the "upload" answers of
+    len(req_ids) messages as websocket frames at the device pointers outs[o],
+    from the names (device, 32 n bytes a message) and body hashes (device, 32
+    bytes a message) save_temp_batch_device left."""
+    ids = np.ascontiguousarray(np.asarray(req_ids, dtype=np.int32).reshape(-1))
+    rs = np.ascontiguousarray(np.asarray(replica_sizes, dtype=np.uint32).reshape(-1))
+    op = np.ascontiguousarray(np.asarray(outs, dtype=np.uint64).reshape(-1))
+    if not (ids.size == rs.size == op.size):
+        raise VdsEcError(_lib.EINVAL, "ws_upload_answer_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_ws_upload_answer_batch_device(
+        ids.size, ids.ctypes.data_as(_lib.i32p), n, _dev_ptr(replica_digests), _dev_ptr(data_digests),
+        rs.ctypes.data_as(_lib.u32p), op.ctypes.data_as(_lib.vpp), _stream_ptr(stream)),
+        "ws_upload_answer_batch_device")
+
+
+def ws_upload_batch(frames: Sequence, k: int = 32, n: int = 64) -> list:
+    """vds_ec_ws_upload16_host_batch: the live upload for a batch of websocket
+    FRAMES, unmasked, decoded, encoded, named and answered on the device.  Per
+    frame a dict with "status" and "answer" (the answer frame's bytes, or None
+    for a frame that got no device work: EWS_SHORT, EWS_FRAME, EWS_PING,
+    EWS_FORM) and, with status 0, what upload_batch returns but "json"."""
+    raws = [bytes(f) for f in frames]
+    count = len(raws)
+    lib = _lib.lib()
+    # room for every replica: a body is shorter than 3/4 of its frame
+    Ls = [replica_size(k, len(r) // 4 * 3) for r in raws]
+    outs = [[np.empty(max(L, 1), dtype=np.uint8) for _ in range(n)] for L in Ls]
+    cap = sum(ws_upload_answer_size(-1, n, 0xFFFFFFFF)[0] for _ in raws)
+    ans = np.zeros(max(1, cap), dtype=np.uint8)
+    rd = np.empty((max(1, count * n), 32), dtype=np.uint8)
+    dd = np.empty((max(1, count), 32), dtype=np.uint8)
+    rs = np.zeros(max(1, count), dtype=np.uint32)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    ao = np.zeros(max(1, count), dtype=np.uint64)
+    al = np.zeros(max(1, count), dtype=np.uint64)
+    fl = np.asarray([len(r) for r in raws] or [0], dtype=np.uint64)
+    failed = C.c_uint32(0)
+    fp = (C.c_char_p * max(1, count))(*raws)
+    op = (C.c_void_p * max(1, count * n))(*[o.ctypes.data for os_ in outs for o in os_])
+    check(lib.vds_ec_ws_upload16_host_batch(k, n, count, C.cast(fp, _lib.vpp), fl.ctypes.data_as(_lib.u64p), op,
+                                            rd.ctypes.data, dd.ctypes.data, rs.ctypes.data_as(_lib.u32p),
+                                            ans.ctypes.data, ans.size, ao.ctypes.data_as(_lib.u64p),
+                                            al.ctypes.data_as(_lib.u64p), st.ctypes.data_as(_lib.i32p),
+                                            C.byref(failed)), "ws_upload16_host_batch")
+    res = []
+    for o in range(count):
+        r = {"status": int(st[o]), "answer": bytes(ans[int(ao[o]):int(ao[o] + al[o])]) if al[o] else None}
+        if not st[o]:
+            names = [bytes(x) for x in rd[o * n:(o + 1) * n]]
+            r.update({"replicas": [x[:int(rs[o])] for x in outs[o]], "tmp_names": tmp_names(names),
+                      "replica_digests": names, "data_hash": bytes(dd[o]), "replica_size": int(rs[o])})
+        res.append(r)
+    return res
+
+
+def ws_download_batch(k: int, req_ids: Sequence[int], horcruxes: Sequence[Mapping[int, object]],
+                      names: Sequence[Sequence[bytes]], witnesses: Sequence | None = None) -> list:
+    """vds_ec_ws_download16_host_batch: download_batch answering in websocket
+    frames.  Returns per object (frame bytes, status, survivor verdicts): the
+    answer frame {"id":"N","result":"<base64>"} when the status is 0, else the
+    error frame."""
+    count = len(horcruxes)
+    items = [list(h.items())[:k] for h in horcruxes]
+    if any(len(it) < k for it in items) or len(names) != count or len(req_ids) != count or \
+            (witnesses is not None and len(witnesses) != count):
+        raise VdsEcError(_lib.EINVAL, "ws_download_batch")
+    ids = _ids([r for it in items for r, _ in it], 2)
+    bufs = [[_u8(v) for _, v in it] for it in items]
+    if any(b.size != bs[0].size for bs in bufs for b in bs):
+        raise VdsEcError(_lib.EINVAL, "ws_download_batch")
+    cs = np.asarray([bs[0].size for bs in bufs] or [0], dtype=np.uint64)
+    sn = np.ascontiguousarray(np.frombuffer(b"".join(bytes(x) for row in names for x in row), dtype=np.uint8))
+    if sn.size != 32 * count * k:
+        raise VdsEcError(_lib.EINVAL, "ws_download_batch: names does not hold one name per survivor")
+    wi = wn = None
+    if witnesses is not None:
+        wi = _ids([w for w, _ in witnesses], 2)
+        wn = np.ascontiguousarray(np.frombuffer(b"".join(bytes(x) for _, x in witnesses), dtype=np.uint8))
+        if wn.size != 32 * count:
+            raise VdsEcError(_lib.EINVAL, "ws_download_batch: one (id, name) per object")
+    rid = np.asarray(list(req_ids) or [0], dtype=np.int32)
+    # (E <= chunk_size * k; an error answer is shorter than 128 bytes)
+    cap = sum(max(ws_download_answer_layout(int(rid[o]), int(cs[o]) * k)[0], 128) for o in range(count))
+    slab = np.zeros(max(1, cap), dtype=np.uint8)
+    fo = np.zeros(max(1, count), dtype=np.uint64)
+    fl = np.zeros(max(1, count), dtype=np.uint64)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    sv = np.zeros(max(1, count * k), dtype=np.uint8)
+    failed = C.c_uint32(0)
+    cp = (C.c_void_p * max(1, count * k))(*[b.ctypes.data for bs in bufs for b in bs])
+    check(_lib.lib().vds_ec_ws_download16_host_batch(
+        k, count, rid.ctypes.data_as(_lib.i32p), _idp(ids, 2), cp, cs.ctypes.data_as(_lib.u64p),
+        sn.ctypes.data if sn.size else None, _idp(wi, 2) if wi is not None and count else None,
+        wn.ctypes.data if wn is not None and count else None, slab.ctypes.data, slab.size,
+        fo.ctypes.data_as(_lib.u64p), fl.ctypes.data_as(_lib.u64p), st.ctypes.data_as(_lib.i32p), sv.ctypes.data,
+        C.byref(failed)), "ws_download16_host_batch")
+    return [(bytes(slab[int(fo[o]):int(fo[o] + fl[o])]), int(st[o]), [int(v) for v in sv[o * k:(o + 1) * k]])
+            for o in range(count)]

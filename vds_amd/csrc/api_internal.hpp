@@ -14,6 +14,8 @@
 //                       name, check);
 //   api_upload_batch.cpp  base64 wire text decoded and encoded on the device,
 //                       and the batched upload from text (decode, save_temp);
+//   api_ws_batch.cpp    websocket frames: the upload loop from frames to answer
+//                       frames, the download loop answering in frames;
 //   api_download_batch.cpp  the download loop in one call: the name check
 //                       (survivors or a witness), the batched restore and the
 //                       gated base64 encode (device and host);
@@ -216,8 +218,32 @@ int repair_host_batch(uint32_t k, uint32_t count, const uint16_t *nodes, const u
                       const uint64_t *chunk_sizes, uint32_t nt, const uint16_t *targets, uint8_t *const *outs,
                       uint8_t *digests, const uint8_t *expected, uint8_t *verdicts, uint32_t *mismatches);
 // base64 wire text on the device (api_upload_batch.cpp, base64.hip)
+// The messages of one decode launch before they are ordered (masks: empty, or
+// one little-endian word of four mask bytes a message).  Kept per thread, so a
+// caller's loop allocates nothing after its first call.
+struct B64DecScratch {
+  std::vector<B64DecMsg> msgs;
+  std::vector<uint32_t> masks;
+  std::vector<uint32_t> key, order, bucket;
+};
+B64DecScratch &b64_dec_scratch();
+int launch_decode(B64DecScratch &sc, hipStream_t s);
 int base64_decode_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
-                               uint8_t *const *outs, const uint64_t *out_sizes, int32_t *statuses, hipStream_t s);
+                               const uint8_t *masks, bool masked, uint8_t *const *outs, const uint64_t *out_sizes,
+                               int32_t *statuses, hipStream_t s);
+// websocket frames in, answer frames out (api_ws_batch.cpp)
+int ws_upload_answer_batch_device(uint32_t count, const int32_t *ids, uint32_t n, const uint8_t *replica_digests,
+                                  const uint8_t *data_digests, const uint32_t *replica_sizes, uint8_t *const *outs,
+                                  hipStream_t s);
+int ws_upload_host_batch(uint32_t k, uint32_t n, uint32_t count, const uint8_t *const *frames,
+                         const uint64_t *frame_lens, uint8_t *const *outs, uint8_t *replica_digests,
+                         uint8_t *data_digests, uint32_t *replica_sizes, uint8_t *answers, uint64_t answers_bytes,
+                         uint64_t *answer_offs, uint64_t *answer_lens, int32_t *statuses, uint32_t *failed);
+int ws_download_host_batch(uint32_t k, uint32_t count, const int32_t *ids, const uint16_t *nodes,
+                           const uint8_t *const *chunks, const uint64_t *chunk_sizes, const uint8_t *survivor_names,
+                           const uint16_t *witness_ids, const uint8_t *witness_names, uint8_t *slab,
+                           uint64_t slab_bytes, uint64_t *frame_offs, uint64_t *frame_lens, int32_t *statuses,
+                           uint8_t *survivor_verdicts, uint32_t *failed);
 int base64_encode_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, char *const *outs,
                                hipStream_t s);
 int upload_host_batch(uint32_t k, uint32_t n, uint32_t count, const char *const *texts, const uint64_t *text_lens,

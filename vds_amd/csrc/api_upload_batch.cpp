@@ -27,12 +27,7 @@ uint64_t decoded_size(const char *t, uint64_t len) {
   return len / 4 * 3 - p;
 }
 
-// The messages of one decode launch before they are ordered.  Kept per
-// thread, so a caller's loop allocates nothing after its first call.
-struct B64DecScratch {
-  std::vector<B64DecMsg> msgs;
-  std::vector<uint32_t> key, order, bucket;
-};
+}  // namespace
 
 B64DecScratch &b64_dec_scratch() {
   thread_local B64DecScratch sc;
@@ -44,10 +39,13 @@ B64DecScratch &b64_dec_scratch() {
 // once.  Equal keys keep the caller's order.  A counting sort where the steps
 // are few against the batch (the upload loop: 16,384 texts of up to 86
 // steps), else a comparison sort.  Then the table in one ring slot and the
-// launch.
+// launch.  With masks (one word a message, beside msgs) the table of masks
+// follows the messages' in the slot, in the same order, and the launch is the
+// masked instance.
 int launch_decode(B64DecScratch &sc, hipStream_t s) {
   const size_t nm = sc.msgs.size();
   if (nm == 0) return VDS_EC_OK;
+  const bool masked = !sc.masks.empty();
   sc.key.resize(nm);
   sc.order.resize(nm);
   uint32_t kmax = 0;
@@ -65,24 +63,31 @@ int launch_decode(B64DecScratch &sc, hipStream_t s) {
     std::stable_sort(sc.order.begin(), sc.order.end(),
                      [&](uint32_t a, uint32_t b) { return sc.msgs[a].len > sc.msgs[b].len; });
   }
-  const size_t bytes = nm * sizeof(B64DecMsg);
+  const size_t o_masks = nm * sizeof(B64DecMsg);
+  const size_t bytes = o_masks + (masked ? nm * sizeof(uint32_t) : 0);
   ParamSlot *slot = nullptr;
   hipError_t e = param_acquire_n(1, &bytes, &slot);
   if (e != hipSuccess) return hip_status(e);
   B64DecMsg *t = reinterpret_cast<B64DecMsg *>(slot->h);
   for (size_t j = 0; j < nm; ++j) t[j] = sc.msgs[sc.order[j]];
+  if (masked) {
+    uint32_t *mk = reinterpret_cast<uint32_t *>(slot->h + o_masks);
+    for (size_t j = 0; j < nm; ++j) mk[j] = sc.masks[sc.order[j]];
+  }
   e = param_commit(slot, bytes, s);
-  if (e == hipSuccess) e = launch_b64_decode_batch(reinterpret_cast<const B64DecMsg *>(slot->d), (uint32_t)nm, s);
+  if (e == hipSuccess)
+    e = masked ? launch_b64_decode_masked_batch(reinterpret_cast<const B64DecMsg *>(slot->d),
+                                                reinterpret_cast<const uint32_t *>(slot->d + o_masks), (uint32_t)nm, s)
+               : launch_b64_decode_batch(reinterpret_cast<const B64DecMsg *>(slot->d), (uint32_t)nm, s);
   const hipError_t re = param_release(slot, s);  // (its event follows whatever was enqueued)
   return hip_status(e != hipSuccess ? e : re);
 }
 
-}  // namespace
-
 int base64_decode_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
-                               uint8_t *const *outs, const uint64_t *out_sizes, int32_t *statuses, hipStream_t s) {
+                               const uint8_t *masks, bool masked, uint8_t *const *outs, const uint64_t *out_sizes,
+                               int32_t *statuses, hipStream_t s) {
   if (count >= (1u << 30)) return VDS_EC_EINVAL;
-  if (count && (!texts || !text_lens || !outs || !out_sizes || !statuses)) return VDS_EC_EINVAL;
+  if (count && (!texts || !text_lens || !outs || !out_sizes || !statuses || (masked && !masks))) return VDS_EC_EINVAL;
   for (uint32_t o = 0; o < count; ++o) {
     if (text_lens[o] > 0xFFFFFFFFull || !decoded_size_legal(text_lens[o], out_sizes[o])) return VDS_EC_EINVAL;
     if ((text_lens[o] && !texts[o]) || (out_sizes[o] && !outs[o])) return VDS_EC_EINVAL;
@@ -95,6 +100,11 @@ int base64_decode_batch_device(uint32_t count, const char *const *texts, const u
   for (uint32_t o = 0; o < count; ++o)
     sc.msgs[o] = B64DecMsg{reinterpret_cast<uintptr_t>(texts[o]), reinterpret_cast<uintptr_t>(outs[o]),
                            reinterpret_cast<uintptr_t>(statuses + o), (uint32_t)text_lens[o], (uint32_t)out_sizes[o]};
+  sc.masks.clear();
+  if (masked) {
+    sc.masks.resize(count);
+    std::memcpy(sc.masks.data(), masks, 4ull * count);  // (bytes 0..3 of a mask: a little-endian word)
+  }
   return launch_decode(sc, s);
 }
 
@@ -228,6 +238,7 @@ int upload_host_batch(uint32_t k, uint32_t n, uint32_t count, const char *const 
                              (uint32_t)size[j]};
       for (uint32_t i = 0; i < n; ++i) d_outs[(size_t)j * n + i] = st->d_out + out_off[j] + i * L[j];
     }
+    sc.masks.clear();
     if ((rc = launch_decode(sc, st->stream))) return drained(rc);
     rc = save_temp_batch_device(k, n, cnt, d_ins.data(), size.data(), d_outs.data(), st->d_out + rd_off,
                                 data_digests ? st->d_out + dd_off : nullptr, st->stream);
@@ -268,7 +279,14 @@ extern "C" {
 int vds_ec_base64_decode_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
                                       uint8_t *const *outs, const uint64_t *out_sizes, int32_t *statuses,
                                       void *stream) {
-  return vds_ec::api::base64_decode_batch_device(count, texts, text_lens, outs, out_sizes, statuses,
+  return vds_ec::api::base64_decode_batch_device(count, texts, text_lens, nullptr, false, outs, out_sizes, statuses,
+                                                 vds_ec::api::as_stream(stream));
+}
+
+int vds_ec_base64_decode_masked_batch_device(uint32_t count, const char *const *texts, const uint64_t *text_lens,
+                                             const uint8_t *masks, uint8_t *const *outs, const uint64_t *out_sizes,
+                                             int32_t *statuses, void *stream) {
+  return vds_ec::api::base64_decode_batch_device(count, texts, text_lens, masks, true, outs, out_sizes, statuses,
                                                  vds_ec::api::as_stream(stream));
 }
 

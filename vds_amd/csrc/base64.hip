@@ -135,8 +135,26 @@ __device__ __forceinline__ void store_run(uint64_t a, const uint32_t (&w)[NW], u
   }
 }
 
-__global__ __launch_bounds__(64) void k_b64_decode_batch(const B64DecMsg *msgs) {
+// MASKED (texts still under their websocket mask, websocket.cpp:162-171):
+// masks[blockIdx.x] beside msgs[blockIdx.x], the four mask bytes of the text's
+// characters 0..3 in a little-endian word; character j is byte j of the text
+// ^ mask byte j & 3.  Everything the kernel looks at is unmasked first.  A
+// lane's 16 characters start at a multiple of 16, so once load_chars has
+// realigned them every dword of the 16 takes the same word.  Unmasked, `masks`
+// is not read and the kernel is the one it was before the mask existed.
+// (a: the character's address, j: its index in the text modulo 4)
+template <bool MASKED>
+__device__ __forceinline__ uint32_t char_at(uint64_t a, uint32_t j, uint32_t mk) {
+  const uint32_t c = byte_at(a);
+  if constexpr (MASKED) return c ^ ((mk >> (8u * (j & 3u))) & 0xFFu);
+  return c;
+}
+
+template <bool MASKED>
+__global__ __launch_bounds__(64) void k_b64_decode_batch(const B64DecMsg *msgs, const uint32_t *masks) {
   const B64DecMsg m = msgs[blockIdx.x];
+  uint32_t mk = 0;
+  if constexpr (MASKED) mk = masks[blockIdx.x];
   const uint32_t lane = threadIdx.x;
   const uint32_t len = m.len;
   const gptr_wi32 status = reinterpret_cast<gptr_wi32>(m.status);
@@ -149,7 +167,10 @@ __global__ __launch_bounds__(64) void k_b64_decode_batch(const B64DecMsg *msgs) 
     return;
   }
   // the '=' among the last two characters against the size the caller declared
-  const uint32_t padding = byte_at(m.text + len - 1) != '=' ? 0u : byte_at(m.text + len - 2) != '=' ? 1u : 2u;
+  const uint32_t padding =
+      char_at<MASKED>(m.text + len - 1, len - 1, mk) != '='   ? 0u
+      : char_at<MASKED>(m.text + len - 2, len - 2, mk) != '=' ? 1u
+                                                              : 2u;
   if (len / 4 * 3 - padding != m.size) {
     if (lane == 0) *status = VDS_EC_EINVAL;
     return;
@@ -159,7 +180,8 @@ __global__ __launch_bounds__(64) void k_b64_decode_batch(const B64DecMsg *msgs) 
   const uint32_t steps = (len - 1) / kB64DecStep + 1;
   u32x4 nx = load_chars(m.text, p, sh, len, 16u * lane);
   for (uint32_t it = 0; it < steps; ++it) {
-    const u32x4 w = nx;
+    u32x4 w = nx;
+    if constexpr (MASKED) w ^= mk;
     const uint64_t c0 = (uint64_t)it * kB64DecStep + 16u * lane;
     if (it + 1 < steps) nx = load_chars(m.text, p, sh, len, c0 + kB64DecStep);
     uint32_t b[4], t[4];
@@ -185,7 +207,7 @@ __global__ __launch_bounds__(64) void k_b64_decode_batch(const B64DecMsg *msgs) 
     const uint32_t fl = (uint32_t)__builtin_ctzll(events);
     const uint32_t e = (uint32_t)__shfl((int)(__builtin_ctz(bad | 0x10000u)), (int)fl);
     const uint32_t pos = it * kB64DecStep + 16u * fl + e;
-    if (byte_at(m.text + pos) != '=') {
+    if (char_at<MASKED>(m.text + pos, pos, mk) != '=') {
       if (lane == 0) *status = VDS_EC_EB64_CHAR;
       return;
     }
@@ -199,7 +221,7 @@ __global__ __launch_bounds__(64) void k_b64_decode_batch(const B64DecMsg *msgs) 
     uint32_t temp = 0;
 #pragma unroll
     for (uint32_t j = 1; j <= 3; ++j)
-      if (pos >= j) temp |= (sextet(byte_at(m.text + pos - j)) & 63u) << (6u * j);
+      if (pos >= j) temp |= (sextet(char_at<MASKED>(m.text + pos - j, pos - j, mk)) & 63u) << (6u * j);
     const uint32_t off = pos / 4 * 3;
     const gptr_w8 out = reinterpret_cast<gptr_w8>(m.out);
     if (lane == 0) {
@@ -298,11 +320,120 @@ __global__ __launch_bounds__(256) void k_b64_encode_batch(const B64EncMsg *msgs,
   }
 }
 
+// The first nb <= 4 NW bytes of w[0..NW) to address a, any nb: the head up to
+// the next aligned address and the tail as bytes, the dwords between them
+// realigned with v_perm_b32.
+template <int NW>
+__device__ __forceinline__ void store_any(uint64_t a, const uint32_t (&w)[NW], uint32_t nb) {
+  const uint32_t h = min((uint32_t)(-a) & 3u, nb);  // head bytes
+  const gptr_w8 b = reinterpret_cast<gptr_w8>(a);
+#pragma unroll
+  for (uint32_t i = 0; i < 3; ++i)
+    if (i < h) b[i] = (uint8_t)(w[0] >> (8 * i));
+  const uint32_t nd = (nb - h) / 4;  // whole dwords behind the head
+  const gptr_w32 d = reinterpret_cast<gptr_w32>(a + h);
+  const uint32_t sel = 0x03020100u + 0x01010101u * h;
+  uint32_t tw = 0;  // the dword behind them, of which the tail is the low bytes
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    const uint32_t v = __builtin_amdgcn_perm(i + 1 < NW ? w[i + 1] : 0u, w[i], sel);
+    if ((uint32_t)i < nd) d[i] = v;
+    if ((uint32_t)i == nd) tw = v;
+  }
+  const uint32_t t0 = h + 4 * nd;
+#pragma unroll
+  for (uint32_t i = 0; i < 3; ++i)
+    if (t0 + i < nb) b[t0 + i] = (uint8_t)(tw >> (8 * i));
+}
+
+// The 44 characters of a 32-byte digest at any address d (base64::from_bytes:
+// ten groups of three bytes, then two bytes and one '='), first character in
+// the low byte of ch[0].  Reads the aligned words holding a digest byte.
+__device__ __forceinline__ void digest_chars(uint64_t dg, uint32_t (&ch)[11]) {
+  const uint32_t sh = (uint32_t)(dg & 3u);
+  const gptr_u32 p = reinterpret_cast<gptr_u32>(dg - sh);
+  const uint32_t sel = 0x03020100u + 0x01010101u * sh;
+  uint32_t raw[9], d[9];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) raw[i] = p[i];
+  raw[8] = sh ? p[8] : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d[i] = __builtin_amdgcn_perm(raw[i + 1], raw[i], sel);
+  d[8] = 0u;
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    const int i = 3 * g, c = 4 * g;
+    ch[c] = b64_chars(__builtin_amdgcn_perm(0u, d[i], 0x0c000102u));
+    ch[c + 1] = b64_chars(__builtin_amdgcn_perm(d[i + 1], d[i], 0x0c030405u));
+    ch[c + 2] = b64_chars(__builtin_amdgcn_perm(d[i + 2], d[i + 1], 0x0c020304u));
+    if (g < 2) ch[c + 3] = b64_chars(__builtin_amdgcn_perm(0u, d[i + 2], 0x0c010203u));
+  }
+  ch[10] = (ch[10] & 0x00FFFFFFu) | 0x3D000000u;  // bytes 30, 31 and one '='
+}
+
+// k_ws_upload_answer_batch: the "upload" answers of `count` messages as
+// websocket frames (vds_ec_ws_frame_header + vds_ec_upload_response_json), ONE
+// WAVE PER MESSAGE.  Every name is 44 characters, so with the frame header and
+// the digits of the id (m.head) and of the replica size (m.tail) given, every
+// piece has its place: lane i < n writes "<name i>" and the comma behind it
+// (none behind the last), lane n the head, ],"hash":"<body hash> and the tail.
+// A lane encodes one digest and waits for no other.
+__global__ __launch_bounds__(256) void k_ws_upload_answer_batch(const WsAnsMsg *msgs, uint32_t count) {
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + threadIdx.x / 64u);
+  if (wv >= count) return;
+  const uint32_t lane = threadIdx.x % 64u;
+  const WsAnsMsg *m = msgs + wv;
+  const uint32_t n = m->n, hl = m->head_len;
+  const uint64_t out = m->out;
+  for (uint32_t i = lane; i <= n; i += 64u) {
+    uint32_t ch[11];
+    if (i < n) {
+      digest_chars(m->rdig + 32ull * i, ch);
+      uint32_t w[12];
+      w[0] = '"' | (ch[0] << 8);
+#pragma unroll
+      for (int j = 1; j < 11; ++j) w[j] = (ch[j - 1] >> 24) | (ch[j] << 8);
+      w[11] = (ch[10] >> 24) | ('"' << 8) | (',' << 16);
+      store_any(out + hl + 47ull * i, w, i + 1 < n ? 47u : 46u);
+    } else {
+      uint32_t hw[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) hw[j] = m->head[j];
+      store_any(out, hw, hl);
+      digest_chars(m->ddig, ch);
+      uint32_t w[22];
+      w[0] = 0x68222C5Du;  // ],"h
+      w[1] = 0x22687361u;  // ash"
+      w[2] = 0x0000223Au | (ch[0] << 16);  // :"
+#pragma unroll
+      for (int j = 1; j < 11; ++j) w[2 + j] = (ch[j - 1] >> 16) | (ch[j] << 16);
+      w[13] = (ch[10] >> 16) | (m->tail[0] << 16);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w[14 + j] = (m->tail[j] >> 16) | (m->tail[j + 1] << 16);
+      store_any(out + hl + (n ? 47ull * n - 1 : 0), w, 54u + m->tail_len);
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t launch_b64_decode_batch(const B64DecMsg *msgs, uint32_t count, hipStream_t s) {
   if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_b64_decode_batch, dim3(count), dim3(64), 0, s, msgs);
+  hipLaunchKernelGGL(k_b64_decode_batch<false>, dim3(count), dim3(64), 0, s, msgs,
+                     static_cast<const uint32_t *>(nullptr));
+  return hipGetLastError();
+}
+
+hipError_t launch_b64_decode_masked_batch(const B64DecMsg *msgs, const uint32_t *masks, uint32_t count,
+                                          hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_b64_decode_batch<true>, dim3(count), dim3(64), 0, s, msgs, masks);
+  return hipGetLastError();
+}
+
+hipError_t launch_ws_upload_answer_batch(const WsAnsMsg *msgs, uint32_t count, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ws_upload_answer_batch, dim3((count + 3) / 4), dim3(256), 0, s, msgs, count);
   return hipGetLastError();
 }
 

@@ -180,6 +180,24 @@ struct B64EncGate {
   uint32_t ngate;
   uint32_t reserved;
 };
+// The "upload" answer of one message as a websocket frame (base64.hip,
+// k_ws_upload_answer_batch: one wave a message).  The few bytes that vary in
+// length come from the host: head = the frame header and {"id":"<id>","result":
+// {"replicas":[ (head_len <= 61 bytes), tail = ","replica_size":"<size>"}}
+// (tail_len <= 31 bytes), both as little-endian words, zero behind their end.
+struct WsAnsMsg {
+  uint64_t out;   // the frame, any alignment
+  uint64_t rdig;  // n digests of 32 bytes back to back, any alignment
+  uint64_t ddig;  // the body's digest
+  uint32_t n;
+  uint32_t head_len;
+  uint32_t tail_len;
+  uint32_t reserved;
+  uint32_t head[16];
+  uint32_t tail[9];
+  uint32_t pad[3];
+};
+static_assert(sizeof(WsAnsMsg) == 152, "WsAnsMsg layout");
 
 // Node-to-node datagrams (dgram.hip): HMAC-SHA256 under a session key, one
 // lane per message or datagram.  The key pads are hashed once per session ON
@@ -495,6 +513,11 @@ void hmac_sha256_host_midstates(const uint8_t *key, size_t key_len, uint32_t inn
 void hmac_sha256_host(const uint8_t *key, size_t key_len, const uint8_t *data, uint64_t len, uint8_t mac[32]);
 // base64 -> bytes of msgs[0..count) (device table), every status written (base64.hip).
 hipError_t launch_b64_decode_batch(const B64DecMsg *msgs, uint32_t count, hipStream_t s);
+// The same for texts under their websocket masks: masks[w] beside msgs[w].
+hipError_t launch_b64_decode_masked_batch(const B64DecMsg *msgs, const uint32_t *masks, uint32_t count,
+                                          hipStream_t s);
+// The "upload" answer frames of msgs[0..count) (device table).
+hipError_t launch_ws_upload_answer_batch(const WsAnsMsg *msgs, uint32_t count, hipStream_t s);
 // bytes -> base64 over tiles[0..ntiles) of msgs (device tables).
 hipError_t launch_b64_encode_batch(const B64EncMsg *msgs, const B64EncTile *tiles, uint32_t ntiles, hipStream_t s);
 // The same behind gates[0..) (beside msgs); every message's status written by its tile 0.

@@ -1018,6 +1018,10 @@ const char *vds_ec_strerror(int status) {
     case VDS_EC_EDGRAM_SIGNATURE: return "Invalid signature";
     case VDS_EC_EDGRAM_DATA: return "Invalid data";
     case VDS_EC_EDGRAM_INCOMPLETE: return "message incomplete: a datagram is missing or did not verify";
+    case VDS_EC_EWS_SHORT: return "websocket frame incomplete";
+    case VDS_EC_EWS_FRAME: return "Not implemented";
+    case VDS_EC_EWS_FORM: return "not the fast form of an upload request";
+    case VDS_EC_EWS_PING: return "websocket ping";
     default: return "unknown vds_ec status";
   }
 }

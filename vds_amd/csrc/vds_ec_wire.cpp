@@ -56,9 +56,184 @@ int copy_out(const std::string &s, char *out, size_t cap, size_t *out_len) {
   return VDS_EC_OK;
 }
 
+// json_object::add_property(name, int) stores std::to_string of the value as
+// vds_ec_upload_response_json prints it: a negative id as its 64-bit two's
+// complement.
+std::string id_text(int id) { return std::to_string((uint64_t)(int64_t)id); }
+
+// json_writer::write_string's escapes (json_writer.cpp:205-240), without the quotes
+std::string json_escaped(const char *s) {
+  static const char kHex[] = "0123456789abcdef";
+  std::string o;
+  for (; *s; ++s) {
+    const unsigned char ch = (unsigned char)*s;
+    switch (ch) {
+      case '\\': o += "\\\\"; break;
+      case '"': o += "\\\""; break;
+      case '\n': o += "\\n"; break;
+      case '\r': o += "\\r"; break;
+      case '\b': o += "\\b"; break;
+      case '\t': o += "\\t"; break;
+      case '\f': o += "\\f"; break;
+      default:
+        if (ch >= 0x20 && ch < 0x7F) {
+          o += (char)ch;
+        } else {
+          o += "\\u00";
+          o += kHex[ch >> 4];
+          o += kHex[ch & 15];
+        }
+    }
+  }
+  return o;
+}
+
+uint32_t ws_header(uint64_t payload_len, bool binary, uint8_t out[10]) {
+  out[0] = binary ? 0x82 : 0x81;
+  if (payload_len < 126) {
+    out[1] = (uint8_t)payload_len;
+    return 2;
+  }
+  if (payload_len <= 0xFFFF) {
+    out[1] = 126;
+    out[2] = (uint8_t)(payload_len >> 8);
+    out[3] = (uint8_t)payload_len;
+    return 4;
+  }
+  out[1] = 127;
+  for (int i = 0; i < 8; ++i) out[2 + i] = (uint8_t)(payload_len >> (56 - 8 * i));
+  return 10;
+}
+
+const char kUpReqHead[] = "{\"id\":";
+const char kUpReqMid[] = ",\"invoke\":\"upload\",\"params\":[\"";
+const char kUpReqTail[] = "\"]}";
+const char kAnsHead[] = "{\"id\":\"";
+const char kUpAnsMid[] = "\",\"result\":{\"replicas\":[";
+const char kUpAnsHash[] = "],\"hash\":\"";
+const char kUpAnsSize[] = "\",\"replica_size\":\"";
+const char kUpAnsTail[] = "\"}}";
+const char kDownAnsMid[] = "\",\"result\":\"";
+const char kErrAnsMid[] = "\",\"error\":\"";
+const char kAnsTail[] = "\"}";
+template <size_t N>
+constexpr size_t lit(const char (&)[N]) {
+  return N - 1;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vds_ec_ws_frame_parse(const uint8_t *buf, size_t len, vds_ec_ws_frame *frame) {
+  if ((len && !buf) || !frame) return VDS_EC_EINVAL;
+  std::memset(frame, 0, sizeof(*frame));
+  if (len < 2) {
+    frame->need = 2;
+    return VDS_EC_EWS_SHORT;
+  }
+  const bool masked = (buf[1] & 0x80) != 0;
+  const uint32_t l7 = buf[1] & 0x7F;
+  const uint32_t off = l7 == 126 ? 4 : l7 == 127 ? 10 : 2;
+  const uint32_t hdr = off + (masked ? 4 : 0);
+  if (len < hdr) {
+    frame->need = hdr;
+    return VDS_EC_EWS_SHORT;
+  }
+  frame->fin = (buf[0] & 0x80) != 0;
+  frame->rsv1 = (buf[0] & 0x40) != 0;
+  frame->rsv2 = (buf[0] & 0x20) != 0;
+  frame->rsv3 = (buf[0] & 0x10) != 0;
+  frame->opcode = buf[0] & 0x0F;
+  frame->masked = masked;
+  frame->header_len = frame->need = hdr;
+  uint64_t pl = l7;
+  if (l7 == 126) {
+    pl = (uint64_t)buf[2] << 8 | buf[3];
+  } else if (l7 == 127) {
+    pl = 0;
+    for (int i = 0; i < 8; ++i) pl = pl << 8 | buf[2 + i];
+  }
+  frame->payload_len = pl;
+  if (masked) std::memcpy(frame->mask, buf + off, 4);
+  return frame->opcode == 1 || frame->opcode == 2 || frame->opcode == 9 ? VDS_EC_OK : VDS_EC_EWS_FRAME;
+}
+
+int vds_ec_ws_frame_header(uint64_t payload_len, int binary, uint8_t out[10], uint32_t *len) {
+  if (!out || !len) return VDS_EC_EINVAL;
+  *len = ws_header(payload_len, binary != 0, out);
+  return VDS_EC_OK;
+}
+
+int vds_ec_ws_upload_request(const uint8_t *payload, uint64_t len, const uint8_t *mask, int32_t *id,
+                             uint64_t *body_off, uint64_t *body_len, uint64_t *decoded_size) {
+  if ((len && !payload) || !id || !body_off || !body_len || !decoded_size) return VDS_EC_EINVAL;
+  const uint8_t zero[4] = {0, 0, 0, 0};
+  const uint8_t *mk = mask ? mask : zero;
+  // the envelope's front: 6 + at most 10 digits + 30 = 46 bytes, and two more
+  uint8_t head[48];
+  const size_t nh = (size_t)(len < sizeof(head) ? len : sizeof(head));
+  for (size_t j = 0; j < nh; ++j) head[j] = payload[j] ^ mk[j & 3];
+  size_t at = lit(kUpReqHead);
+  if (nh < at + 1 || std::memcmp(head, kUpReqHead, at)) return VDS_EC_EWS_FORM;
+  uint64_t v = 0;
+  size_t nd = 0;
+  while (at + nd < nh && nd < 11 && head[at + nd] >= '0' && head[at + nd] <= '9') v = v * 10 + (head[at + nd++] - '0');
+  if (nd == 0 || nd > 10 || (nd > 1 && head[at] == '0') || v > 0x7FFFFFFFull) return VDS_EC_EWS_FORM;
+  at += nd;
+  if (nh < at + lit(kUpReqMid) || std::memcmp(head + at, kUpReqMid, lit(kUpReqMid))) return VDS_EC_EWS_FORM;
+  at += lit(kUpReqMid);
+  if (len < at + lit(kUpReqTail)) return VDS_EC_EWS_FORM;
+  // the envelope's end and the body's last two characters
+  const uint64_t blen = len - at - lit(kUpReqTail);
+  uint8_t tail[5];
+  for (uint64_t j = len - 5; j < len; ++j) tail[j - (len - 5)] = payload[j] ^ mk[j & 3];  // (len >= 40)
+  if (std::memcmp(tail + 2, kUpReqTail, lit(kUpReqTail))) return VDS_EC_EWS_FORM;
+  uint64_t size = 0;
+  if (blen && blen % 4 == 0) size = blen / 4 * 3 - (tail[1] != '=' ? 0 : tail[0] != '=' ? 1 : 2);
+  *id = (int32_t)v;
+  *body_off = at;
+  *body_len = blen;
+  *decoded_size = size;
+  return VDS_EC_OK;
+}
+
+int vds_ec_ws_upload_answer_size(int id, uint32_t n, uint32_t replica_size, uint64_t *frame_len,
+                                 uint32_t *header_len) {
+  const uint64_t json = lit(kAnsHead) + id_text(id).size() + lit(kUpAnsMid) + 46ull * n + (n ? n - 1 : 0) +
+                        lit(kUpAnsHash) + 44 + lit(kUpAnsSize) + std::to_string((uint64_t)replica_size).size() +
+                        lit(kUpAnsTail);
+  uint8_t h[10];
+  const uint32_t hl = ws_header(json, false, h);
+  if (frame_len) *frame_len = hl + json;
+  if (header_len) *header_len = hl;
+  return VDS_EC_OK;
+}
+
+int vds_ec_ws_download_answer_layout(int id, uint64_t object_size, uint64_t *frame_len, uint32_t *header_len,
+                                     uint64_t *text_off) {
+  if (object_size > 0xFFFFFFFFFFFFFF00ull / 2) return VDS_EC_EINVAL;
+  const uint64_t front = lit(kAnsHead) + id_text(id).size() + lit(kDownAnsMid);
+  const uint64_t json = front + (object_size + 2) / 3 * 4 + lit(kAnsTail);
+  uint8_t h[10];
+  const uint32_t hl = ws_header(json, false, h);
+  if (frame_len) *frame_len = hl + json;
+  if (header_len) *header_len = hl;
+  if (text_off) *text_off = hl + front;
+  return VDS_EC_OK;
+}
+
+int vds_ec_ws_error_answer(int id, int status, uint8_t *out, size_t cap, size_t *out_len) {
+  const std::string json = kAnsHead + id_text(id) + kErrAnsMid + json_escaped(vds_ec_strerror(status)) + kAnsTail;
+  uint8_t h[10];
+  const uint32_t hl = ws_header(json.size(), false, h);
+  if (out_len) *out_len = hl + json.size();
+  if (!out) return VDS_EC_OK;  // size query
+  if (cap < hl + json.size()) return VDS_EC_EINVAL;
+  std::memcpy(out, h, hl);
+  std::memcpy(out + hl, json.data(), json.size());
+  return VDS_EC_OK;
+}
 
 size_t vds_ec_base64_decoded_size(const char *in, size_t len) {
   if (!in || len % 4) return 0;
