@@ -32,7 +32,10 @@ p.add_argument("--k", type=int, default=16, choices=(16, 32))
 p.add_argument("--jit", action="store_true")
 a = p.parse_args()
 if a.jit:  # phases of the fill + two-level interpolation kernel (restore_syn.hpp marks)
-    PHASES = ["stage1 transposes+puts", "B1", "-", "-", "-", "scatter fill", "B(fill)", "S1 (levels 1-2)", "B(S1)",
+    # (the inbox form, vds_ec_jit.cpp VDS_JIT_INBOX: stage 1 has no puts and no B1, the fill's shares go
+    # to the owners' inboxes, and S1 starts with the inbox reads)
+    PHASES = ["stage1 transposes(+puts)", "B1 (inbox form: none)", "-", "-", "-", "scatter / inbox fill + load issue",
+              "B(fill)", "S1 (levels 1-2)", "B(S1)",
               "S2 (families)", "B(S2)", "S3 + puts", "B(S3)", "stage C", "B(stage C read) + late loads",
               "staging transposes+writes", "B(staging)", "copy-out stores", "B(tile end)", "-"]
 k, n, size = a.k, a.k + a.k // 4, 64 << 20
@@ -65,10 +68,10 @@ per_block = total_tiles / grid
 st = buf[: grid * WV * NPH].reshape(grid, WV, NPH).astype(np.float64) / per_block
 tot = st[:, :, :19].sum(axis=2).mean()
 print(f"{total_tiles} tiles, {per_block:.1f} per block; mean s_memtime ticks per tile: {tot:.0f}")
-print(f"{'phase':28s} " + " ".join(f"{'w%d' % w:>8s}" for w in range(WV)) + f" {'mean':>8s} {'%':>6s}")
+print(f"{'phase':34s} " + " ".join(f"{'w%d' % w:>8s}" for w in range(WV)) + f" {'mean':>8s} {'%':>6s}")
 for ph in range(19):
     col = st[:, :, ph].mean(axis=0)
-    print(f"{PHASES[ph]:28s} " + " ".join(f"{c:8.0f}" for c in col) + f" {col.mean():8.0f} {100 * col.mean() / tot:6.1f}")
+    print(f"{PHASES[ph]:34s} " + " ".join(f"{c:8.0f}" for c in col) + f" {col.mean():8.0f} {100 * col.mean() / tot:6.1f}")
 
 # Phase coherence across CUs (slots 20..23: s_memrealtime, the chip-global
 # 100 MHz clock, at wave 0's survivor-load issue of its tiles 4, 64, 160, 240).

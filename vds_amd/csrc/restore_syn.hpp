@@ -278,6 +278,38 @@ struct S1In {
   }
 };
 
+// Inbox fill (FillP::kInbox, xorprog.hpp emit_fill_inbox; k = 16 survivor
+// sets with at most one erased point below K in each interpolation group).
+// Wave W loads its own group's survivors, plus one survivor >= K when the
+// group has an erased point, in the order FillP::kSurv[4 W ..] (launch rank
+// order(4 W + s)), and keeps them in registers: stage 1 stores nothing.
+template <class F, class = void>
+struct FillInbox {
+  static constexpr bool value = false;
+  __device__ __forceinline__ static int order(int j) { return j; }
+};
+template <class F>
+struct FillInbox<F, decltype(void(F::kInbox))> {
+  static constexpr bool value = F::kInbox;
+  __device__ __forceinline__ static int order(int j) { return (int)((F::kOrderPack >> (4 * j)) & 15u); }
+};
+// S1's input with all four points of group W from registers: the survivors
+// from stage 1's planes, the erased point (if any) from `own`.
+template <class FillP, int W>
+struct S1Regs {
+  const Plane16 (&P)[4];
+  const Plane16 &own;
+  __device__ __forceinline__ u32x4 operator()(int g) const {
+    const int pt = g >> 2, q = g & 3;
+    int i = -1;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (FillP::kSurv[4 * W + s] == pt) i = s;
+    if (i < 0) return u32x4{own.p[4 * q], own.p[4 * q + 1], own.p[4 * q + 2], own.p[4 * q + 3]};
+    return u32x4{P[i].p[4 * q], P[i].p[4 * q + 1], P[i].p[4 * q + 2], P[i].p[4 * q + 3]};
+  }
+};
+
 // Two-level interpolation (VDS_GM2, default; generated gm_* programs,
 // tools/xorgen/gen_restore.cpp emit_gm2): levels 1 and 2 of the additive FFT
 // on each wave's own four slots (S1, in place), the K/4-point direct
@@ -307,27 +339,30 @@ struct S1In {
 #define VDS_HALF_PRIO 1
 #endif
 // OwnP (not void): the own-group fill's policy; `own` is this wave's group's
-// erased point, which S1 takes from registers.
-template <int K, int N, int WV, int W, class Tail, class OwnP = void>
+// erased point, which S1 takes from registers.  S1 = false (the inbox fill):
+// S1 has run already (syn_inbox_s1 below) and its output is in the slots.
+template <int K, int N, int WV, int W, class Tail, class OwnP = void, bool S1 = true>
 __device__ __forceinline__ void syn_interp_gm2(int wave, const SynLds &L, Stamps &st, Tail &&tail,
                                                const Plane16 *own = nullptr) {
   using P = RestorePrograms<K, N, WV>;
   constexpr bool kPrio = SynShape<K, N, WV>::kPrio;
   constexpr int H = K / 2, kWpf = WV / 4, kWpq = WV / 2;
   if constexpr (W < WV) {
-    if (wave != W) return syn_interp_gm2<K, N, WV, W + 1, Tail &, OwnP>(wave, L, st, tail, own);
+    if (wave != W) return syn_interp_gm2<K, N, WV, W + 1, Tail &, OwnP, S1>(wave, L, st, tail, own);
     uint32_t cells[16 * (K / WV)];
     uint32_t acc[64];
     auto cell = [&](int c) -> uint32_t(&)[16] { return *reinterpret_cast<uint32_t(*)[16]>(acc + 16 * c); };
-    // S1: levels 1 and 2 on this wave's slots 4W..4W+3 (only this wave touches them)
-    syn_prio<1, kPrio && (VDS_GM2_PRIO & 1)>();
-    if constexpr (__is_same(OwnP, void))
-      P::gm_s1_(W, L, acc);
-    else
-      P::gm_s1_(W, S1In<OwnP::kPoint[W]>{L, *own}, acc);
+    if constexpr (S1) {
+      // S1: levels 1 and 2 on this wave's slots 4W..4W+3 (only this wave touches them)
+      syn_prio<1, kPrio && (VDS_GM2_PRIO & 1)>();
+      if constexpr (__is_same(OwnP, void))
+        P::gm_s1_(W, L, acc);
+      else
+        P::gm_s1_(W, S1In<OwnP::kPoint[W]>{L, *own}, acc);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) syn_put_point(L, 4 * W + c, cell(c));
-    syn_prio<0, kPrio && (VDS_GM2_PRIO & 1)>();
+      for (int c = 0; c < 4; ++c) syn_put_point(L, 4 * W + c, cell(c));
+      syn_prio<0, kPrio && (VDS_GM2_PRIO & 1)>();
+    }
     st.mark(7);
     __syncthreads();
     st.mark(8);
@@ -590,6 +625,66 @@ __device__ __forceinline__ void syn_own_fill(int wave, const SynLds &L, const Pl
   }
 }
 
+// Inbox fill (FillInbox above): wave W's share of every erased point below K
+// from its four stage-1 registers -- the scatter fill's column partition over
+// the group-aligned ownership.  The share of its own group's erased point
+// stays in registers (`own`); the share of group g's goes with plain stores
+// into slot 4 g + W, wave g's inbox from wave W.  Nobody zeroes the inboxes:
+// before the fill barrier only the other waves write wave g's slots, after
+// it only wave g reads them (syn_inbox_s1) and then stores its S1 output
+// over them; the previous tile's reads of the slots end at its last barrier.
+template <int WV, class FillP, int W>
+__device__ __forceinline__ void syn_inbox_fill(int wave, const SynLds &L, const Plane16 (&Ps)[4], Plane16 &own) {
+  if constexpr (W < WV) {
+    if (wave != W) return syn_inbox_fill<WV, FillP, W + 1>(wave, L, Ps, own);
+    static_assert(FillP::kParts <= 1 && FillP::kFill <= WV, "at most one erased point per group");
+    if constexpr (FillP::kFill > 0) {
+      uint32_t acc[16 * FillP::kPart];
+      FillP::fill_part(0, W, FillRegIn<FillP, W>{Ps}, acc);
+#pragma unroll
+      for (int m = 0; m < FillP::kFill; ++m) {
+        const Plane16 &v = *reinterpret_cast<const Plane16 *>(acc + 16 * m);
+        if (m == FillP::kOwnM[W])
+          own = v;
+        else
+          syn_put_point(L, 4 * (FillP::kPoint[m] / 4) + W, v.p);
+      }
+    }
+  }
+}
+
+// S1 of the inbox form, after the fill barrier: wave W completes its group's
+// erased point -- its own share plus the three in its inbox -- and runs
+// levels 1 and 2 on its four points from registers (S1Regs), storing the
+// output into its slots 4W..4W+3 as syn_interp_gm2's S1 does.  In a dispatch
+// of its own, not in syn_interp_gm2's arms: there, with the next tile's
+// survivor loads issued before it as now, the kernel spilled 92-132 VGPRs,
+// and with the loads issued inside each arm after S1's stores up to 519 (the
+// loaded registers merge at the arms' join).
+template <int K, int N, int WV, class FillP, int W>
+__device__ __forceinline__ void syn_inbox_s1(int wave, const SynLds &L, const Plane16 (&Ps)[4], const Plane16 &own) {
+  if constexpr (W < WV) {
+    if (wave != W) return syn_inbox_s1<K, N, WV, FillP, W + 1>(wave, L, Ps, own);
+    constexpr bool kPrio = SynShape<K, N, WV>::kPrio;
+    syn_prio<1, kPrio && (VDS_GM2_PRIO & 1)>();
+    Plane16 mine;  // (never read when the group has no erased point)
+    if constexpr (FillP::kOwnM[W] >= 0) {
+      static_assert(WV == 4, "three incoming shares");
+      uint32_t in[WV - 1][16];
+#pragma unroll
+      for (int w = 0; w < WV; ++w)
+        if (w != W) syn_get_point(L, 4 * W + w, in[w < W ? w : w - 1]);
+#pragma unroll
+      for (int b = 0; b < 16; ++b) mine.p[b] = xor3(own.p[b], in[0][b], in[1][b]) ^ in[2][b];
+    }
+    uint32_t acc[64];
+    RestorePrograms<K, N, WV>::gm_s1_(W, S1Regs<FillP, W>{Ps, mine}, acc);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) syn_put_point(L, 4 * W + c, *reinterpret_cast<uint32_t(*)[16]>(acc + 16 * c));
+    syn_prio<0, kPrio && (VDS_GM2_PRIO & 1)>();
+  }
+}
+
 // Batch mode: the last tile of an object may run past its bytes.  Loads
 // beyond `valid` bytes read zeros and stores beyond it write nothing (byte by
 // byte for the one 16-byte piece that straddles the end).
@@ -707,9 +802,11 @@ template <int K, int MS> struct SmallSyn;
 template <int K, int N, int WV, bool REGEN, bool BATCH, bool RT = false, class FillP = NoFill>
 __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
   constexpr bool FILL = FillP::kFill >= 0;
-  constexpr bool kScatter = FILL && FillP::kScatter;
+  constexpr bool kInbox = FILL && FillInbox<FillP>::value;
+  constexpr bool kScatter = FILL && FillP::kScatter && !kInbox;
   constexpr bool kOwn = FILL && FillOwn<FillP>::value;
   static_assert(!kOwn || (K == 16 && !REGEN && !BATCH && !RT), "the own-group fill is a k = 16 restore form");
+  static_assert(!kInbox || (K == 16 && !REGEN && !BATCH && !RT && VDS_GM2 != 0), "the inbox fill is a k = 16 restore form");
   constexpr bool kSmall = FillP::kSmall;
   constexpr bool kPerm = FillP::kPerm;
   constexpr bool kMulti = FillP::kMulti;
@@ -776,7 +873,9 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
       const uint64_t st0 = stripe0_of(t);
 #pragma unroll
       for (int s = 0; s < S::kLoadPer; ++s) {
-        const uint8_t *src = a.chunks[wave * S::kLoadPer + s] + (uint64_t)ob * a.chunk_stride + 2 * st0 + 16 * lane;
+        // (the inbox fill: this wave's survivors by its ownership table)
+        const uint8_t *src = a.chunks[FillInbox<FillP>::order(wave * S::kLoadPer + s)] +
+                             (uint64_t)ob * a.chunk_stride + 2 * st0 + 16 * lane;
 #pragma unroll
         for (int q = 0; q < 4; ++q) Q[s][q] = g_ld<4, u32x4>(src + 1024 * q);
       }
@@ -845,8 +944,8 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
     const int my_erased = RT ? K + wave : perm_tile ? K : (wave < S::kM ? erased_of(wave) : 0);
     // RT: this wave's slots, kept for phase 2; the scatter fill: its survivors (VDS_FILL_REGS)
     constexpr bool kFillRegs = kScatter && VDS_FILL_REGS && K == 16;
-    constexpr bool kKeepPs = RT || kFillRegs || kOwn;
-    Plane16 own;  // (own-group fill: this wave's group's erased point)
+    constexpr bool kKeepPs = RT || kFillRegs || kOwn || kInbox;
+    Plane16 own;  // (own-group fill: this wave's group's erased point; inbox fill: this wave's share of it)
     static_assert(!kKeepPs || S::kLoadPer == 4, "four survivors per wave");
     Plane16 Ps[kKeepPs ? S::kLoadPer : 1];
 
@@ -923,6 +1022,9 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
               for (int b = 0; b < 16; ++b) Pl[b] &= keep;
             syn_put_point(L, j, Pl);
           }
+        } else if constexpr (kInbox) {  // (registers only: nothing stored, nothing for a barrier to publish)
+#pragma unroll
+          for (int b = 0; b < 16; ++b) Ps[s].p[b] = Pl[b];
         } else {
           if constexpr (kKeepPs)
 #pragma unroll
@@ -942,10 +1044,20 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
           }
         }
       }
+      if constexpr (kInbox) {
+        // Nothing is stored here that would hold the transposes inside the
+        // priority window: without these (empty, ordered) statements the
+        // compiler moved them behind the s_setprio 0 below, and stage 1 ran
+        // at priority 0.
+#pragma unroll
+        for (int s = 0; s < S::kLoadPer; ++s)
+#pragma unroll
+          for (int b = 0; b < 16; ++b) asm volatile("" : "+v"(Ps[s].p[b]));
+      }
     }
     syn_prio<0, kPrio>();
     st.mark(0);
-    __syncthreads();
+    if constexpr (!kInbox) __syncthreads();  // (inbox fill: stage 1 stored nothing)
     st.mark(1);
     // phase-2 bodies, shared by the single-class kernels and MULTI
     auto phase_perm = [&](auto tag) {
@@ -1373,6 +1485,16 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
       else
         syn_scatter_fill<WV, FillP, false, 0>(wave, L, {});
       if (!kLateLoad) prefetch(tile + t_step);
+    } else if constexpr (kInbox) {
+      // ---- 2 (inbox). this wave's survivors' share of every erased point
+      // below K: its own group's into `own`, the others' into their inboxes
+      syn_inbox_fill<WV, FillP, 0>(wave, L, Ps, own);
+      // (where the scatter form issues them.  Before the fill: 142-160 VGPRs
+      // spilled.  After S1: no spill either, but the loads' shorter window
+      // cost more than the form saves -- same box, ABBA, 1024 x 64 MiB:
+      // repair 27.11-27.24 ms against the scatter form's 26.94-26.99, and
+      // here 25.78-25.86 against 26.86-26.93, profiles/jit_inbox)
+      prefetch(tile + t_step);
     } else if constexpr (kOwn) {
       // ---- 2 (own). this wave's group's erased point, kept in registers for S1
       syn_own_fill<WV, FillP, 0>(wave, L, Ps, own);
@@ -1402,7 +1524,9 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
       phase_syn();
     }  // (phase 2)
     st.mark(5);
-    if constexpr (!kOwn) __syncthreads();  // (own-group fill: S1 reads only what stage 1 published)
+    // (own-group fill: S1 reads only what stage 1 published; inbox fill with
+    // no erased point below K: S1 reads registers only)
+    if constexpr (!kOwn && !(kInbox && FillP::kFill == 0)) __syncthreads();
     st.mark(6);
     if constexpr (REGEN) {
       // ---- 3'. regenerate: the recovered point e_w IS replica e_w's cells
@@ -1487,7 +1611,7 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
       // vector spill of before).  The other kernels keep the join: with the
       // tail in the branches the plain k = 32 kernel spilled 1,844 (the late
       // loads beside the staging).
-      constexpr bool kTailInWave = RT || kFillRegs || kOwn;
+      constexpr bool kTailInWave = RT || kFillRegs || kOwn || kInbox;
       auto tail = [&](uint32_t (&cells)[16 * S::kCells]) {
       if (kLateLoad && !BATCH) prefetch(tile + t_step);
       // this wave's copy-out: 1024 kChunks bytes at wofs of the tile's output
@@ -1632,7 +1756,11 @@ __device__ __forceinline__ void restore_syn_body(const SynRestoreArgs &a) {
         st.mark(17);
       }
       };
-      if constexpr (VDS_GM2 != 0 && kOwn) {
+      if constexpr (VDS_GM2 != 0 && kInbox) {
+        static_assert(!kLateLoad, "the inbox form issues the next tile's loads after its fill");
+        syn_inbox_s1<K, N, WV, FillP, 0>(wave, L, Ps, own);
+        syn_interp_gm2<K, N, WV, 0, decltype(tail) &, void, false>(wave, L, st, tail);
+      } else if constexpr (VDS_GM2 != 0 && kOwn) {
         syn_interp_gm2<K, N, WV, 0, decltype(tail) &, FillP>(wave, L, st, tail, &own);
       } else if constexpr (VDS_GM2 != 0 && kTailInWave) {
         syn_interp_gm2<K, N, WV, 0>(wave, L, st, tail);

@@ -104,6 +104,24 @@ constexpr bool fill_scatter() { return VDS_JIT_SCATTER != 0; }
 #ifndef VDS_JIT_OWN
 #define VDS_JIT_OWN 0
 #endif
+// The inbox fill (xorprog.hpp emit_fill_inbox) for k = 16 restore sets with
+// at most one erased point below k in each interpolation group, e.g. the
+// headline set: group-aligned survivor ownership, no stage-1 stores, and S1
+// from registers.  -DVDS_JIT_INBOX=0 builds the scatter form for those sets
+// too (A/B); VDS_EC_JIT_INBOX=0 / 1 in the environment overrides the build's
+// choice for one process.  The cache is keyed by the source, so the two
+// forms' code objects coexist.
+#ifndef VDS_JIT_INBOX
+#define VDS_JIT_INBOX 1
+#endif
+bool fill_inbox() {
+  static const bool on = [] {
+    const char *v = std::getenv("VDS_EC_JIT_INBOX");
+    if (v && (!std::strcmp(v, "0") || !std::strcmp(v, "1"))) return v[0] == '1';
+    return VDS_JIT_INBOX != 0;
+  }();
+  return on;
+}
 
 // JIT policy: 0 = off, 1 = background compile from a set's second use
 // (default), 2 = compile on the calling thread at the first use.  Initially
@@ -178,6 +196,8 @@ std::string kernel_source(const Key &key) {
     xorgen::emit_fill_scatter(s, "JitFill", K, sp, &tg);
   } else if (VDS_JIT_OWN && xorgen::fill_own_eligible(K, sp)) {
     xorgen::emit_fill_own(s, "JitFill", K, sp, fill_block(), fill_prefetch());
+  } else if (fill_scatter() && fill_inbox() && xorgen::fill_inbox_eligible(K, sp)) {
+    xorgen::emit_fill_inbox(s, "JitFill", K, sp);
   } else if (fill_scatter()) {
     xorgen::emit_fill_scatter(s, "JitFill", K, sp);
   } else {

@@ -389,8 +389,9 @@ static_assert(VDS_JIT_SPB >= 1 && VDS_JIT_SPB <= 4, "scatter block size");
 constexpr int scatter_block() { return VDS_JIT_SPB; }
 // `targets` (optional): the points to compute instead of the erased points
 // below K -- the regenerate kernel's targets, every erased point of 0..N-1.
+// `extra` (optional): further members of the struct (emit_fill_inbox).
 inline size_t emit_fill_scatter(std::string &s, const char *name, int K, const std::vector<int> &spoints,
-                                const std::vector<int> *targets = nullptr) {
+                                const std::vector<int> *targets = nullptr, const std::string *extra = nullptr) {
   std::vector<int> EU;
   if (targets) {
     EU = *targets;
@@ -422,6 +423,7 @@ inline size_t emit_fill_scatter(std::string &s, const char *name, int K, const s
   appendf(s, "  static constexpr uint8_t kSurv[%d] = {", K);
   for (int j = 0; j < K; ++j) appendf(s, "%d, ", spoints[j]);
   appendf(s, "};\n");
+  if (extra) s += *extra;
   size_t total = 0;
   for (int w = 0; w < WV; ++w)
     for (int q = 0; q < parts; ++q) {
@@ -513,6 +515,57 @@ inline size_t emit_fill_own(std::string &s, const char *name, int K, const std::
   for (int m = 0; m < F; ++m) appendf(s, "    %sif constexpr (W == %d) own%d(IN4, acc);\n", m ? "else " : "", m, m);
   appendf(s, "  }\n};\n");
   return total;
+}
+
+// "Inbox" fill of one survivor set (k = 16, four waves; restore only): for
+// sets with at most one erased point below K in every interpolation group
+// {4g..4g+3}.  Wave g loads its own group's survivors (three or four) and,
+// when the group has an erased point, one survivor >= K -- there are as many
+// of those as erased points below K, so every wave loads four -- and keeps
+// them in registers through S1, which then reads no survivor back from LDS.
+// The fill is the scatter form's column partition over that ownership: wave
+// w's share of its own group's erased point stays in registers, its share of
+// another group's goes with plain stores into an inbox (slot 4 owner + w)
+// that only the owner reads (restore_syn.hpp kInbox): no zeroed slots, no LDS
+// atomics, no barrier after stage 1.  kSurv is in ownership order (wave w:
+// entries 4w..4w+3, the group's survivors ascending, then the one >= K),
+// kOrderPack holds the rank (among the survivors sorted by point, the
+// launch's order) of entry j in bits 4j..4j+3, and kOwnM[g] is the index in
+// kPoint of group g's erased point, or -1.
+inline bool fill_inbox_eligible(int K, const std::vector<int> &spoints) {
+  if (K != 16 || (int)spoints.size() != K) return false;
+  for (int g = 0; g < K / 4; ++g) {
+    int e = 0;
+    for (int a = 4 * g; a < 4 * g + 4; ++a) e += std::find(spoints.begin(), spoints.end(), a) == spoints.end();
+    if (e > 1) return false;
+  }
+  return true;
+}
+inline size_t emit_fill_inbox(std::string &s, const char *name, int K, const std::vector<int> &spoints) {
+  if (!fill_inbox_eligible(K, spoints)) return 0;
+  std::vector<int> sorted = spoints, extras, owned, EU;
+  std::sort(sorted.begin(), sorted.end());
+  for (int p : sorted)
+    if (p >= K) extras.push_back(p);
+  size_t next_extra = 0;
+  std::string extra = "  static constexpr bool kInbox = true;\n  static constexpr int kOwnM[4] = {";
+  for (int g = 0; g < K / 4; ++g) {
+    int have = 0;
+    for (int a = 4 * g; a < 4 * g + 4; ++a)
+      if (std::binary_search(sorted.begin(), sorted.end(), a)) {
+        owned.push_back(a);
+        ++have;
+      } else {
+        EU.push_back(a);
+      }
+    if (have < 4) owned.push_back(extras[next_extra++]);
+    appendf(extra, "%d, ", have < 4 ? (int)EU.size() - 1 : -1);
+  }
+  uint64_t pack = 0;
+  for (int j = 0; j < K; ++j)
+    pack |= (uint64_t)(std::lower_bound(sorted.begin(), sorted.end(), owned[j]) - sorted.begin()) << (4 * j);
+  appendf(extra, "};\n  static constexpr uint64_t kOrderPack = 0x%016llxull;\n", (unsigned long long)pack);
+  return emit_fill_scatter(s, name, K, owned, nullptr, &extra);
 }
 
 }  // namespace xorgen
