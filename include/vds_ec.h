@@ -56,6 +56,10 @@ extern "C" {
 #define VDS_EC_EWS_FRAME (-15) /* "Not implemented" (an opcode other than text, binary and ping)   */
 #define VDS_EC_EWS_FORM (-16)  /* not the fast form of "upload": the caller's own parser decides     */
 #define VDS_EC_EWS_PING (-17)  /* a ping met in a batch: no device work, the caller sends its pong   */
+/* AES-256-CBC decryption (symmetric_decrypt, private/symmetriccrypto_p.h); the reference reports both
+ * as "EVP_CipherFinal_ex failed": */
+#define VDS_EC_ECRYPT_LENGTH (-18)  /* a ciphertext of 0 bytes or not a multiple of 16 (OpenSSL: "wrong final block length") */
+#define VDS_EC_ECRYPT_PADDING (-19) /* last byte not in 1..16, or the last n bytes not all n (OpenSSL: "bad decrypt")       */
 
 /* ----------------------------------------------------------------- flags */
 /* write_padding = false in chunk_generator::write (chunk.h:79,273-278):
@@ -914,6 +918,86 @@ int vds_ec_ws_download16_host_batch(uint16_t k, uint32_t count, const int32_t *i
                                     const uint8_t *witness_names, uint8_t *slab, uint64_t slab_bytes,
                                     uint64_t *frame_offs, uint64_t *frame_lens, int32_t *statuses,
                                     uint8_t *survivor_verdicts, uint32_t *failed);
+
+/* ------------------------------------------------ file blocks: AES-256-CBC
+ * The reference turns a piece of a file into a body and back with AES-256-CBC
+ * under PKCS#7 padding (client::save / restore, dht_network_client.cpp:1101-
+ * 1320; save_block, web/src/store/vds_ws.js:151-161; OpenSSL's EVP default in
+ * private/symmetriccrypto_p.h):
+ *     id      = SHA-256(data)
+ *     key     = SHA-256(AES-256-CBC(id, pack_block_iv, data))
+ *     crypted = AES-256-CBC(key, pack_block_iv, deflate(data))
+ * and back: decrypt under key, inflate, SHA-256 == id or "Data is corrupted".
+ * Deflate and inflate stay the caller's (zlib); key does not depend on the
+ * deflate's output.  The same cipher wraps every channel message under its own
+ * key and iv (user_channel.cpp:229).
+ *
+ * vds_ec_aes256_cbc_padded_size: what len bytes encrypt to, (len/16 + 1) * 16.
+ * vds_ec_block_iv: pack_block_iv, a5bb9fce c2e44b91 a8c95944 62559024.
+ * The *_host pair: ONE message on the calling thread, no GPU (AES-NI where the
+ * CPU has it, else portable code; VDS_EC_AES_HOST=portable in the environment
+ * at the first call forces the latter).  Encrypt writes padded_size(len) bytes
+ * at out (in == out allowed).  Decrypt writes up to len bytes at out, of which
+ * the first *out_len are the plaintext, and returns VDS_EC_OK,
+ * VDS_EC_ECRYPT_LENGTH (nothing written) or VDS_EC_ECRYPT_PADDING (*out_len 0). */
+uint64_t vds_ec_aes256_cbc_padded_size(uint64_t len);
+int vds_ec_block_iv(uint8_t iv[16]);
+int vds_ec_aes256_cbc_encrypt_host(const uint8_t key[32], const uint8_t iv[16], const uint8_t *in, uint64_t len,
+                                   uint8_t *out);
+int vds_ec_aes256_cbc_decrypt_host(const uint8_t key[32], const uint8_t iv[16], const uint8_t *in, uint64_t len,
+                                   uint8_t *out, uint64_t *out_len);
+
+/* `count` messages of different lengths in one launch each way.  ins, lens,
+ * outs: HOST arrays of device pointers and lengths, any alignment (fast path:
+ * 16-byte aligned).  keys: DEVICE, count * 32 bytes, 4-byte aligned (message
+ * o's key at keys + 32 o: keys are digests of a hash launch).  ivs: DEVICE,
+ * count * 16 bytes, or NULL: every message under pack_block_iv.  out_lens,
+ * statuses: DEVICE, 4-byte aligned.  Nothing synchronises.  Everything is
+ * validated before anything is enqueued and before the device is looked for:
+ * VDS_EC_EINVAL for null arrays, a null pointer with a non-zero length,
+ * lens[o] >= 2^32, count >= 2^30, a message whose input and output overlap;
+ * count == 0 is VDS_EC_OK.
+ * Encrypt writes exactly padded_size(lens[o]) bytes at outs[o].
+ * Decrypt writes at most lens[o] bytes at outs[o], of which the first
+ * out_lens[o] are the plaintext; every statuses[o] (VDS_EC_OK,
+ * VDS_EC_ECRYPT_LENGTH, VDS_EC_ECRYPT_PADDING) and out_lens[o] is written by
+ * the launch, a bad status with out_len 0 and unspecified contents; a length
+ * that is 0 or no multiple of 16 gets its status and no other work.        */
+int vds_ec_aes256_cbc_encrypt_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                           const uint8_t *keys, const uint8_t *ivs, uint8_t *const *outs,
+                                           void *stream);
+int vds_ec_aes256_cbc_decrypt_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                           const uint8_t *keys, const uint8_t *ivs, uint8_t *const *outs,
+                                           uint32_t *out_lens, int32_t *statuses, void *stream);
+
+/* client::save for `count` blocks on device pointers: four launches on the
+ * stream, no host step between them -- SHA-256 of datas into ids, encrypt
+ * datas under ids into library scratch, SHA-256 of that into keys, encrypt
+ * zipped under keys into crypted[o] (padded_size(zipped_lens[o]) bytes, which
+ * may be handed to vds_ec_save_temp16_batch_device as body o).  ids, keys:
+ * DEVICE, count * 32 bytes each, 4-byte aligned.  zipped[o] is the caller's
+ * deflate of datas[o]; the call does not look inside it.  Validation as above
+ * (a crypted[o] overlapping datas[o] or zipped[o] included).
+ * Unpacking needs no entry of its own: decrypt with ivs == NULL, the caller's
+ * inflate, vds_ec_sha256_check_batch_device against ids.                    */
+int vds_ec_block_pack_batch_device(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                   const uint8_t *const *zipped, const uint64_t *zipped_lens, uint8_t *ids,
+                                   uint8_t *keys, uint8_t *const *crypted, void *stream);
+/* The same on HOST pointers (ids, keys host too): gathered into pinned staging
+ * at 16-byte aligned offsets, one copy in, the device form, one copy back,
+ * scattered; groups of at most 64 MiB; the calling thread's current device;
+ * every block validated before any transfer.  crypted_sizes (may be NULL)
+ * receives padded_size(zipped_lens[o]).                                    */
+int vds_ec_block_pack_host_batch(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                 const uint8_t *const *zipped, const uint64_t *zipped_lens, uint8_t *ids,
+                                 uint8_t *keys, uint8_t *const *crypted, uint64_t *crypted_sizes);
+/* vds_ec_aes256_cbc_decrypt_batch_device on HOST pointers, staged the same
+ * way (keys, ivs host; ivs NULL: pack_block_iv).  outs[o] must hold lens[o]
+ * bytes; a message whose status is not VDS_EC_OK has out_lens[o] 0 and its
+ * output untouched; *failed (may be NULL) counts them.                      */
+int vds_ec_aes256_cbc_decrypt_host_batch(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                         const uint8_t *keys, const uint8_t *ivs, uint8_t *const *outs,
+                                         uint64_t *out_lens, int32_t *statuses, uint32_t *failed);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

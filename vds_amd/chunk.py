@@ -1307,3 +1307,171 @@ def ws_download_batch(k: int, req_ids: Sequence[int], horcruxes: Sequence[Mappin
         C.byref(failed)), "ws_download16_host_batch")
     return [(bytes(slab[int(fo[o]):int(fo[o] + fl[o])]), int(st[o]), [int(v) for v in sv[o * k:(o + 1) * k]])
             for o in range(count)]
+
+
+# ------------------------------------------------------------- file blocks
+def aes256_cbc_padded_size(length: int) -> int:
+    """vds_ec_aes256_cbc_padded_size: what `length` bytes encrypt to under PKCS#7."""
+    return int(_lib.lib().vds_ec_aes256_cbc_padded_size(length))
+
+
+def block_iv() -> bytes:
+    """vds_ec_block_iv: pack_block_iv (dht_network_client.cpp:1101-1105)."""
+    iv = np.zeros(16, dtype=np.uint8)
+    check(_lib.lib().vds_ec_block_iv(iv.ctypes.data), "block_iv")
+    return iv.tobytes()
+
+
+def aes256_cbc_encrypt_host(key, data, iv=None) -> bytes:
+    """vds_ec_aes256_cbc_encrypt_host: one message on the calling thread
+    (symmetric_encrypt::encrypt; iv None: pack_block_iv)."""
+    k, d, v = _u8(key), _u8(data), _u8(block_iv() if iv is None else iv)
+    if k.size != 32 or v.size != 16:
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_encrypt_host: a key of 32 bytes and an iv of 16")
+    out = np.empty(aes256_cbc_padded_size(d.size), dtype=np.uint8)
+    check(_lib.lib().vds_ec_aes256_cbc_encrypt_host(k.ctypes.data, v.ctypes.data, d.ctypes.data if d.size else None,
+                                                    d.size, out.ctypes.data), "aes256_cbc_encrypt_host")
+    return out.tobytes()
+
+
+def aes256_cbc_decrypt_host(key, data, iv=None) -> bytes:
+    """vds_ec_aes256_cbc_decrypt_host: one message on the calling thread
+    (symmetric_decrypt::decrypt); raises VdsEcError with VDS_EC_ECRYPT_LENGTH
+    or VDS_EC_ECRYPT_PADDING where the reference's EVP_CipherFinal_ex fails."""
+    k, d, v = _u8(key), _u8(data), _u8(block_iv() if iv is None else iv)
+    if k.size != 32 or v.size != 16:
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_decrypt_host: a key of 32 bytes and an iv of 16")
+    out = np.empty(max(1, d.size), dtype=np.uint8)
+    n = C.c_uint64(0)
+    check(_lib.lib().vds_ec_aes256_cbc_decrypt_host(k.ctypes.data, v.ctypes.data, d.ctypes.data if d.size else None,
+                                                    d.size, out.ctypes.data, C.byref(n)), "aes256_cbc_decrypt_host")
+    return out[:n.value].tobytes()
+
+
+def _ptr_table(values) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray([_dev_ptr(v) or 0 for v in values], dtype=np.uint64).reshape(-1))
+
+
+def aes256_cbc_encrypt_batch_device(ins, lens, keys, outs, ivs=None, stream=None) -> None:
+    """vds_ec_aes256_cbc_encrypt_batch_device: message o, lens[o] bytes at the
+    device pointer ins[o], encrypted under the 32 bytes at keys + 32 o (device)
+    and the 16 at ivs + 16 o (device; None: pack_block_iv) into
+    aes256_cbc_padded_size(lens[o]) bytes at the device pointer outs[o]; the
+    whole batch in one launch."""
+    ip, op = _ptr_table(ins), _ptr_table(outs)
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ln.size == op.size):
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_encrypt_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_aes256_cbc_encrypt_batch_device(
+        ln.size, ip.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p), _dev_ptr(keys), _dev_ptr(ivs),
+        op.ctypes.data_as(_lib.vpp), _stream_ptr(stream)), "aes256_cbc_encrypt_batch_device")
+
+
+def aes256_cbc_decrypt_batch_device(ins, lens, keys, outs, out_lens, statuses, ivs=None, stream=None) -> None:
+    """vds_ec_aes256_cbc_decrypt_batch_device: the mirror; out_lens (uint32)
+    and statuses (int32) are device buffers of one entry a message, all written
+    by the launch."""
+    ip, op = _ptr_table(ins), _ptr_table(outs)
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ln.size == op.size):
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_decrypt_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_aes256_cbc_decrypt_batch_device(
+        ln.size, ip.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p), _dev_ptr(keys), _dev_ptr(ivs),
+        op.ctypes.data_as(_lib.vpp), _dev_ptr(out_lens), _dev_ptr(statuses), _stream_ptr(stream)),
+        "aes256_cbc_decrypt_batch_device")
+
+
+def block_pack_batch_device(datas, data_lens, zipped, zipped_lens, ids, keys, crypted, stream=None) -> None:
+    """vds_ec_block_pack_batch_device: client::save for a batch of blocks on
+    device pointers -- ids + 32 o = SHA-256(data o), keys + 32 o =
+    SHA-256(AES(id, data)), crypted[o] = AES(key, zipped o), four launches."""
+    dp, zp, cp = _ptr_table(datas), _ptr_table(zipped), _ptr_table(crypted)
+    dl = np.ascontiguousarray(np.asarray(data_lens, dtype=np.uint64).reshape(-1))
+    zl = np.ascontiguousarray(np.asarray(zipped_lens, dtype=np.uint64).reshape(-1))
+    if not (dp.size == dl.size == zp.size == zl.size == cp.size):
+        raise VdsEcError(_lib.EINVAL, "block_pack_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_block_pack_batch_device(
+        dl.size, dp.ctypes.data_as(_lib.vpp), dl.ctypes.data_as(_lib.u64p), zp.ctypes.data_as(_lib.vpp),
+        zl.ctypes.data_as(_lib.u64p), _dev_ptr(ids), _dev_ptr(keys), cp.ctypes.data_as(_lib.vpp),
+        _stream_ptr(stream)), "block_pack_batch_device")
+
+
+def block_pack_host_batch(datas: Sequence, zipped: Sequence) -> list:
+    """vds_ec_block_pack_host_batch: one (id, key, crypted) per block from the
+    blocks and their deflated forms (host bytes)."""
+    ds, zs = [_u8(d) for d in datas], [_u8(z) for z in zipped]
+    count = len(ds)
+    if len(zs) != count:
+        raise VdsEcError(_lib.EINVAL, "block_pack_host_batch: one deflated form per block")
+    dl = np.asarray([d.size for d in ds] or [0], dtype=np.uint64)
+    zl = np.asarray([z.size for z in zs] or [0], dtype=np.uint64)
+    outs = [np.empty(aes256_cbc_padded_size(z.size), dtype=np.uint8) for z in zs]
+    ids = np.empty((max(1, count), 32), dtype=np.uint8)
+    keys = np.empty((max(1, count), 32), dtype=np.uint8)
+    cs = np.zeros(max(1, count), dtype=np.uint64)
+    dp = (C.c_void_p * max(1, count))(*[d.ctypes.data if d.size else None for d in ds])
+    zp = (C.c_void_p * max(1, count))(*[z.ctypes.data if z.size else None for z in zs])
+    cp = (C.c_void_p * max(1, count))(*[o.ctypes.data for o in outs])
+    check(_lib.lib().vds_ec_block_pack_host_batch(count, dp, dl.ctypes.data_as(_lib.u64p), zp,
+                                                  zl.ctypes.data_as(_lib.u64p), ids.ctypes.data, keys.ctypes.data, cp,
+                                                  cs.ctypes.data_as(_lib.u64p)), "block_pack_host_batch")
+    return [(bytes(ids[o]), bytes(keys[o]), outs[o][:int(cs[o])].tobytes()) for o in range(count)]
+
+
+def aes256_cbc_decrypt_host_batch(ins: Sequence, keys: Sequence, ivs: Sequence | None = None) -> list:
+    """vds_ec_aes256_cbc_decrypt_host_batch: per message (plaintext or None,
+    status) -- host ciphertexts decrypted on the device in one call."""
+    cts = [_u8(c) for c in ins]
+    count = len(cts)
+    if len(keys) != count or (ivs is not None and len(ivs) != count):
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_decrypt_host_batch: one key (and iv) per message")
+    kk = np.ascontiguousarray(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8))
+    vv = None if ivs is None else np.ascontiguousarray(np.frombuffer(b"".join(bytes(v) for v in ivs), dtype=np.uint8))
+    if kk.size != 32 * count or (vv is not None and vv.size != 16 * count):
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_decrypt_host_batch: keys of 32 bytes, ivs of 16")
+    ln = np.asarray([c.size for c in cts] or [0], dtype=np.uint64)
+    outs = [np.empty(max(1, c.size), dtype=np.uint8) for c in cts]
+    ol = np.zeros(max(1, count), dtype=np.uint64)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    failed = C.c_uint32(0)
+    ip = (C.c_void_p * max(1, count))(*[c.ctypes.data if c.size else None for c in cts])
+    op = (C.c_void_p * max(1, count))(*[o.ctypes.data for o in outs])
+    check(_lib.lib().vds_ec_aes256_cbc_decrypt_host_batch(
+        count, ip, ln.ctypes.data_as(_lib.u64p), kk.ctypes.data if count else None,
+        vv.ctypes.data if vv is not None and count else None, op, ol.ctypes.data_as(_lib.u64p),
+        st.ctypes.data_as(_lib.i32p), C.byref(failed)), "aes256_cbc_decrypt_host_batch")
+    return [(None if st[o] else outs[o][:int(ol[o])].tobytes(), int(st[o])) for o in range(count)]
+
+
+def block_pack_batch(datas: Sequence, level: int = 6) -> list:
+    """save_block / client::save for a batch of blocks: per block (id, key,
+    crypted) with id = SHA-256(data), key = SHA-256(AES(id, data)) and crypted
+    = AES(key, zlib.compress(data, level)); the hashes and ciphers run on the
+    device (vds_ec_block_pack_host_batch), the deflate here."""
+    import zlib
+    ds = [bytes(_u8(d)) for d in datas]
+    return block_pack_host_batch(ds, [zlib.compress(d, level) for d in ds])
+
+
+def block_unpack_batch(crypted: Sequence, keys: Sequence, ids: Sequence) -> list:
+    """client::restore for a batch of blocks: decrypt under keys on the device
+    (vds_ec_aes256_cbc_decrypt_host_batch), inflate, and compare the SHA-256
+    with ids.  Raises VdsEcError with the first failing block's decrypt status,
+    or VDS_EC_ECORRUPT ("Data is corrupted") where the bytes do not inflate or
+    do not hash to their id."""
+    import hashlib
+    import zlib
+    if len(ids) != len(crypted):
+        raise VdsEcError(_lib.EINVAL, "block_unpack_batch: one id per block")
+    res = []
+    for o, (plain, st) in enumerate(aes256_cbc_decrypt_host_batch(crypted, keys)):
+        if st:
+            raise VdsEcError(st, f"block_unpack_batch: block {o}")
+        try:
+            data = zlib.decompress(plain)
+        except zlib.error:
+            raise VdsEcError(_lib.ECORRUPT, f"block_unpack_batch: block {o} does not inflate") from None
+        if hashlib.sha256(data).digest() != bytes(ids[o]):
+            raise VdsEcError(_lib.ECORRUPT, f"block_unpack_batch: block {o}")
+        res.append(data)
+    return res

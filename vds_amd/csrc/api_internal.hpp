@@ -21,6 +21,9 @@
 //                       gated base64 encode (device and host);
 //   api_dgram_batch.cpp  the node-to-node datagram layer: batched HMAC-SHA256,
 //                       sealing and opening of datagrams (device and host);
+//   api_block_batch.cpp  file blocks: batched AES-256-CBC, the pack of a batch
+//                       of blocks (hash, encrypt, hash, encrypt) and the host
+//                       forms of both;
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once

@@ -180,6 +180,40 @@ struct B64EncGate {
   uint32_t ngate;
   uint32_t reserved;
 };
+// AES-256-CBC over messages of different lengths (aes.hip).  Encrypt: one QUAD
+// per message (a chain), 16 chains a wave, the chains longest first; msgs[q]
+// is quad q's.  Message idx's key is 32 bytes at keys + 32 idx, its iv 16 at
+// ivs + 16 idx (ivs 0: pack_block_iv).
+constexpr uint32_t kAesEncChainsPerWave = 16;
+struct AesEncMsg {
+  uint64_t in;   // len bytes, any alignment; never dereferenced when len == 0
+  uint64_t out;  // (len / 16 + 1) * 16 bytes, any alignment
+  uint32_t len;
+  uint32_t idx;  // the message's place in the caller's order
+};
+// Decrypt: one workgroup of kAesDecThreads lanes per tile of kAesDecTile
+// ciphertext bytes, one lane a 16-byte block a step; tiles[w] = workgroup w's
+// message and its tile of it.  Every message has a tile 0 (one whose length is
+// 0 or no multiple of 16 too: it writes the status and does nothing else).
+constexpr uint32_t kAesDecTile = 16384;
+constexpr uint32_t kAesDecThreads = 256;
+struct AesDecMsg {
+  uint64_t in;   // len bytes, any alignment
+  uint64_t out;  // len bytes, any alignment, not overlapping in
+  uint32_t len;
+  uint32_t reserved;
+};
+struct AesDecTile {
+  uint32_t msg;
+  uint32_t tile;
+};
+struct AesDecLaunch {
+  const AesDecMsg *msgs;
+  const AesDecTile *tiles;
+  uint32_t ntiles;
+  uint64_t keys, ivs;          // as above, by message index
+  uint64_t out_lens, statuses;  // uint32_t / int32_t a message
+};
 // The "upload" answer of one message as a websocket frame (base64.hip,
 // k_ws_upload_answer_batch: one wave a message).  The few bytes that vary in
 // length come from the host: head = the frame header and {"id":"<id>","result":
@@ -523,6 +557,16 @@ hipError_t launch_b64_encode_batch(const B64EncMsg *msgs, const B64EncTile *tile
 // The same behind gates[0..) (beside msgs); every message's status written by its tile 0.
 hipError_t launch_b64_encode_gated_batch(const B64EncMsg *msgs, const B64EncGate *gates, const B64EncTile *tiles,
                                          uint32_t ntiles, hipStream_t s);
+// AES-256-CBC (aes.hip): the chains msgs[0..count) (device table, longest first), keys / ivs by
+// AesEncMsg::idx; lane_chain: one lane a chain instead of one quad (the A/B arm).  And the tiled decrypt.
+hipError_t launch_aes_encrypt_batch(const AesEncMsg *msgs, uint32_t count, const uint8_t *keys, const uint8_t *ivs,
+                                    hipStream_t s, bool lane_chain = false);
+hipError_t launch_aes_decrypt_batch(const AesDecLaunch &l, hipStream_t s);
+// One message on the calling CPU thread (aes_host.cpp); the decrypt returns its status.
+void aes256_cbc_encrypt_host(const uint8_t key[32], const uint8_t iv[16], const uint8_t *in, uint64_t len,
+                             uint8_t *out);
+int aes256_cbc_decrypt_host(const uint8_t key[32], const uint8_t iv[16], const uint8_t *in, uint64_t len, uint8_t *out,
+                            uint64_t *out_len);
 hipError_t launch_fill_splitmix(uint8_t *dst, uint64_t size, uint64_t seed, hipStream_t s);
 // Device -> mapped pinned host copy by a kernel (dst: the device view of the
 // host buffer; both 16-byte aligned).

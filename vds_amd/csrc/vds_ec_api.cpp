@@ -15,7 +15,7 @@ using namespace vds_ec::api;
 namespace vds_ec {
 namespace api {
 
-constexpr int kVersion = 100;  // 0.1.0
+constexpr int kVersion = 101;  // 0.1.1: file blocks (AES-256-CBC, vds_ec_block_pack_*)
 
 
 int hip_status(hipError_t e) {
@@ -1022,6 +1022,8 @@ const char *vds_ec_strerror(int status) {
     case VDS_EC_EWS_FRAME: return "Not implemented";
     case VDS_EC_EWS_FORM: return "not the fast form of an upload request";
     case VDS_EC_EWS_PING: return "websocket ping";
+    case VDS_EC_ECRYPT_LENGTH: return "EVP_CipherFinal_ex failed (wrong final block length)";
+    case VDS_EC_ECRYPT_PADDING: return "EVP_CipherFinal_ex failed (bad decrypt)";
     default: return "unknown vds_ec status";
   }
 }
