@@ -60,6 +60,11 @@ extern "C" {
  * as "EVP_CipherFinal_ex failed": */
 #define VDS_EC_ECRYPT_LENGTH (-18)  /* a ciphertext of 0 bytes or not a multiple of 16 (OpenSSL: "wrong final block length") */
 #define VDS_EC_ECRYPT_PADDING (-19) /* last byte not in 1..16, or the last n bytes not all n (OpenSSL: "bad decrypt")       */
+/* inflate (kernel/vds_data/private/inflate_p.h: zlib's inflate); the reference reports the first as
+ * "inflate failed" and the second not at all: */
+#define VDS_EC_EINFLATE_DATA (-20)  /* what zlib answers Z_DATA_ERROR or Z_NEED_DICT to                     */
+#define VDS_EC_EINFLATE_SHORT (-21) /* the input ends before the stream does; what it held has been delivered */
+#define VDS_EC_EINFLATE_SPACE (-22) /* the plaintext would pass the output's capacity                        */
 
 /* ----------------------------------------------------------------- flags */
 /* write_padding = false in chunk_generator::write (chunk.h:79,273-278):
@@ -928,9 +933,10 @@ int vds_ec_ws_download16_host_batch(uint16_t k, uint32_t count, const int32_t *i
  *     key     = SHA-256(AES-256-CBC(id, pack_block_iv, data))
  *     crypted = AES-256-CBC(key, pack_block_iv, deflate(data))
  * and back: decrypt under key, inflate, SHA-256 == id or "Data is corrupted".
- * Deflate and inflate stay the caller's (zlib); key does not depend on the
- * deflate's output.  The same cipher wraps every channel message under its own
- * key and iv (user_channel.cpp:229).
+ * Deflate stays the caller's (zlib: its output differs between
+ * implementations, and key does not depend on it); the way back is
+ * vds_ec_block_unpack_batch_device below.  The same cipher wraps every channel
+ * message under its own key and iv (user_channel.cpp:229).
  *
  * vds_ec_aes256_cbc_padded_size: what len bytes encrypt to, (len/16 + 1) * 16.
  * vds_ec_block_iv: pack_block_iv, a5bb9fce c2e44b91 a8c95944 62559024.
@@ -977,9 +983,7 @@ int vds_ec_aes256_cbc_decrypt_batch_device(uint32_t count, const uint8_t *const 
  * may be handed to vds_ec_save_temp16_batch_device as body o).  ids, keys:
  * DEVICE, count * 32 bytes each, 4-byte aligned.  zipped[o] is the caller's
  * deflate of datas[o]; the call does not look inside it.  Validation as above
- * (a crypted[o] overlapping datas[o] or zipped[o] included).
- * Unpacking needs no entry of its own: decrypt with ivs == NULL, the caller's
- * inflate, vds_ec_sha256_check_batch_device against ids.                    */
+ * (a crypted[o] overlapping datas[o] or zipped[o] included).               */
 int vds_ec_block_pack_batch_device(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
                                    const uint8_t *const *zipped, const uint64_t *zipped_lens, uint8_t *ids,
                                    uint8_t *keys, uint8_t *const *crypted, void *stream);
@@ -998,6 +1002,77 @@ int vds_ec_block_pack_host_batch(uint32_t count, const uint8_t *const *datas, co
 int vds_ec_aes256_cbc_decrypt_host_batch(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
                                          const uint8_t *keys, const uint8_t *ivs, uint8_t *const *outs,
                                          uint64_t *out_lens, int32_t *statuses, uint32_t *failed);
+
+/* ------------------------------------------------------ file blocks: inflate
+ * The reference's inflate (kernel/vds_data/inflate.h, private/inflate_p.h) is
+ * zlib's: a zlib header, deflate blocks, an Adler-32 trailer (pako.deflate in
+ * the web client writes the same).  Statuses, of one message:
+ *   VDS_EC_OK              the stream ended and its Adler-32 matches; bytes
+ *                          behind the stream's end are ignored; out_len = the
+ *                          plaintext's length.
+ *   VDS_EC_EINFLATE_DATA   zlib's Z_DATA_ERROR or Z_NEED_DICT: a bad header
+ *                          (method, window, check, preset dictionary), block
+ *                          type 3, a stored length that is not its complement's,
+ *                          too many length or distance symbols, an invalid set
+ *                          of code lengths, a repeat with no length before it,
+ *                          no end-of-block code, an invalid literal/length or
+ *                          distance code, a distance reaching before the
+ *                          output's start, a wrong Adler-32.  out_len 0,
+ *                          contents unspecified.
+ *   VDS_EC_EINFLATE_SHORT  the input ends before the stream does.  out_len =
+ *                          what zlib delivers for that input, and those bytes
+ *                          are valid: every literal whose code lies wholly
+ *                          inside the input, every match whose length code,
+ *                          distance code and extra bits lie wholly inside it,
+ *                          the bytes of a stored block that are there.  An
+ *                          error shows only once the bits that reveal it are
+ *                          inside the input.  An input of length 0 is SHORT.
+ *   VDS_EC_EINFLATE_SPACE  the next literal, match or stored run would pass
+ *                          out_cap.  out_len 0, contents unspecified.
+ * No byte is written at or past out + out_cap, whatever the stream says.
+ *
+ * vds_ec_inflate_host: ONE message on the calling thread, no GPU, no zlib.
+ * VDS_EC_EINVAL for a null out_len, a null pointer with a non-zero size, a
+ * size >= 2^32, input and output overlapping.                               */
+int vds_ec_inflate_host(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+/* `count` streams in one launch, one wave a stream.  ins, lens, outs,
+ * out_caps: HOST arrays of device pointers and sizes, any alignment.
+ * out_lens, statuses: DEVICE, 4-byte aligned, every one of them written by
+ * the launch.  Nothing synchronises.  Everything is validated before anything
+ * is enqueued and before the device is looked for: VDS_EC_EINVAL for null
+ * arrays, a null pointer with a non-zero size, lens[o] or out_caps[o] >= 2^32,
+ * count >= 2^30, a message whose input and output overlap; count == 0 is
+ * VDS_EC_OK.                                                                */
+int vds_ec_inflate_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                uint8_t *const *outs, const uint64_t *out_caps, uint32_t *out_lens,
+                                int32_t *statuses, void *stream);
+/* The same on HOST pointers (out_lens, statuses host too), staged through
+ * pinned buffers in groups of at most 64 MiB each way.  A message whose status
+ * is not VDS_EC_OK (VDS_EC_EINFLATE_SHORT included) has out_lens[o] 0 and its
+ * output untouched; *failed (may be NULL) counts them.                      */
+int vds_ec_inflate_host_batch(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                              uint8_t *const *outs, const uint64_t *out_caps, uint64_t *out_lens,
+                              int32_t *statuses, uint32_t *failed);
+/* client::restore (dht_network_client.cpp:1297-1316) for `count` blocks on
+ * device pointers: three launches on the stream, no host step and no
+ * synchronisation between them -- decrypt crypted[o] under keys + 32 o and
+ * pack_block_iv into library scratch, inflate from there into outs[o], SHA-256
+ * of the inflated bytes compared with ids + 32 o.  keys: DEVICE, 4-byte
+ * aligned; ids: DEVICE, any alignment; the rest as the inflate's.
+ * statuses[o] is the first step that failed: VDS_EC_ECRYPT_LENGTH /
+ * VDS_EC_ECRYPT_PADDING, VDS_EC_EINFLATE_DATA / VDS_EC_EINFLATE_SPACE,
+ * VDS_EC_ECORRUPT where the digest differs from the id, else VDS_EC_OK.  A
+ * stream that ends short goes on to the hash, as in the reference, and is OK
+ * only if its bytes hash to the id.  out_lens[o] is 0 for every status but OK. */
+int vds_ec_block_unpack_batch_device(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                                     const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs,
+                                     const uint64_t *out_caps, uint32_t *out_lens, int32_t *statuses, void *stream);
+/* The same on HOST pointers (keys, ids, out_lens, statuses host too), staged
+ * as above.  A block whose status is not VDS_EC_OK has its output untouched;
+ * *failed (may be NULL) counts them.                                        */
+int vds_ec_block_unpack_host_batch(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                                   const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs,
+                                   const uint64_t *out_caps, uint64_t *out_lens, int32_t *statuses, uint32_t *failed);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

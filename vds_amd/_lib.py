@@ -32,6 +32,9 @@ EWS_FORM = -16
 EWS_PING = -17
 ECRYPT_LENGTH = -18
 ECRYPT_PADDING = -19
+EINFLATE_DATA = -20
+EINFLATE_SHORT = -21
+EINFLATE_SPACE = -22
 
 F_NO_TRAILER = 0x1
 F_CELLS = 0x2
@@ -181,6 +184,13 @@ SIGNATURES = {
     "vds_ec_block_pack_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p]),
     "vds_ec_aes256_cbc_decrypt_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p,
                                                        i32p, u32p]),
+    "vds_ec_inflate_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
+    "vds_ec_inflate_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vds_ec_inflate_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, u64p, i32p, u32p]),
+    "vds_ec_block_unpack_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vds_ec_block_unpack_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p, u64p,
+                                                 i32p, u32p]),
     "vds_ec_base64_decoded_size": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "vds_ec_base64_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "vds_ec_base64_encode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

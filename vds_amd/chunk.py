@@ -1443,6 +1443,107 @@ def aes256_cbc_decrypt_host_batch(ins: Sequence, keys: Sequence, ivs: Sequence |
     return [(None if st[o] else outs[o][:int(ol[o])].tobytes(), int(st[o])) for o in range(count)]
 
 
+def inflate_host(data, cap: int) -> tuple:
+    """vds_ec_inflate_host: one zlib stream on the calling thread, no GPU and
+    no zlib -> (status, bytes): the plaintext under VDS_EC_OK, what the input
+    held under VDS_EC_EINFLATE_SHORT, nothing under VDS_EC_EINFLATE_DATA and
+    VDS_EC_EINFLATE_SPACE (`cap`: the output's capacity)."""
+    d = _u8(data)
+    out = np.empty(max(1, cap), dtype=np.uint8)
+    n = C.c_uint64(0)
+    st = _lib.lib().vds_ec_inflate_host(d.ctypes.data if d.size else None, d.size, out.ctypes.data if cap else None,
+                                        cap, C.byref(n))
+    if st not in (_lib.OK, _lib.EINFLATE_DATA, _lib.EINFLATE_SHORT, _lib.EINFLATE_SPACE):
+        check(st, "inflate_host")
+    return int(st), out[:n.value].tobytes()
+
+
+def inflate_batch_device(ins, lens, outs, out_caps, out_lens, statuses, stream=None) -> None:
+    """vds_ec_inflate_batch_device: stream o, lens[o] bytes at the device
+    pointer ins[o], inflated into at most out_caps[o] bytes at the device
+    pointer outs[o]; out_lens (uint32) and statuses (int32) are device buffers
+    of one entry a stream, all written by the one launch."""
+    ip, op = _ptr_table(ins), _ptr_table(outs)
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    cp = np.ascontiguousarray(np.asarray(out_caps, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ln.size == op.size == cp.size):
+        raise VdsEcError(_lib.EINVAL, "inflate_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_inflate_batch_device(
+        ln.size, ip.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+        cp.ctypes.data_as(_lib.u64p), _dev_ptr(out_lens), _dev_ptr(statuses), _stream_ptr(stream)),
+        "inflate_batch_device")
+
+
+def _unpack_outs(caps):
+    outs = [np.full(max(1, int(c)), 0xA5, dtype=np.uint8) for c in caps]
+    return outs, (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+
+
+def inflate_host_batch(ins: Sequence, caps: Sequence) -> list:
+    """vds_ec_inflate_host_batch: per stream (plaintext or None, status) --
+    host streams inflated on the device in one call; caps[o] is stream o's
+    capacity."""
+    zs = [_u8(z) for z in ins]
+    count = len(zs)
+    if len(caps) != count:
+        raise VdsEcError(_lib.EINVAL, "inflate_host_batch: one capacity per stream")
+    ln = np.asarray([z.size for z in zs] or [0], dtype=np.uint64)
+    cp = np.asarray([int(c) for c in caps] or [0], dtype=np.uint64)
+    outs, op = _unpack_outs(caps)
+    ol = np.zeros(max(1, count), dtype=np.uint64)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    failed = C.c_uint32(0)
+    ip = (C.c_void_p * max(1, count))(*[z.ctypes.data if z.size else None for z in zs])
+    check(_lib.lib().vds_ec_inflate_host_batch(count, ip, ln.ctypes.data_as(_lib.u64p), op,
+                                               cp.ctypes.data_as(_lib.u64p), ol.ctypes.data_as(_lib.u64p),
+                                               st.ctypes.data_as(_lib.i32p), C.byref(failed)), "inflate_host_batch")
+    return [(None if st[o] else outs[o][:int(ol[o])].tobytes(), int(st[o])) for o in range(count)]
+
+
+def block_unpack_batch_device(crypted, crypted_lens, keys, ids, outs, out_caps, out_lens, statuses,
+                              stream=None) -> None:
+    """vds_ec_block_unpack_batch_device: client::restore for a batch of blocks
+    on device pointers -- decrypt crypted[o] under keys + 32 o, inflate into
+    outs[o] (at most out_caps[o] bytes), SHA-256 against ids + 32 o; three
+    launches, statuses (int32) and out_lens (uint32) on the device."""
+    ip, op = _ptr_table(crypted), _ptr_table(outs)
+    ln = np.ascontiguousarray(np.asarray(crypted_lens, dtype=np.uint64).reshape(-1))
+    cp = np.ascontiguousarray(np.asarray(out_caps, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ln.size == op.size == cp.size):
+        raise VdsEcError(_lib.EINVAL, "block_unpack_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_block_unpack_batch_device(
+        ln.size, ip.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p), _dev_ptr(keys), _dev_ptr(ids),
+        op.ctypes.data_as(_lib.vpp), cp.ctypes.data_as(_lib.u64p), _dev_ptr(out_lens), _dev_ptr(statuses),
+        _stream_ptr(stream)), "block_unpack_batch_device")
+
+
+def block_unpack_host_batch(crypted: Sequence, keys: Sequence, ids: Sequence, caps: Sequence) -> list:
+    """vds_ec_block_unpack_host_batch: per block (data or None, status) -- host
+    bodies decrypted, inflated and checked against their ids on the device in
+    one call; caps[o] is block o's capacity.  Unlike block_unpack_batch it
+    raises for no block: a failed one has its status."""
+    cts = [_u8(c) for c in crypted]
+    count = len(cts)
+    if not (len(keys) == len(ids) == len(caps) == count):
+        raise VdsEcError(_lib.EINVAL, "block_unpack_host_batch: one key, id and capacity per block")
+    kk = np.ascontiguousarray(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8))
+    ii = np.ascontiguousarray(np.frombuffer(b"".join(bytes(i) for i in ids), dtype=np.uint8))
+    if kk.size != 32 * count or ii.size != 32 * count:
+        raise VdsEcError(_lib.EINVAL, "block_unpack_host_batch: keys and ids of 32 bytes")
+    ln = np.asarray([c.size for c in cts] or [0], dtype=np.uint64)
+    cp = np.asarray([int(c) for c in caps] or [0], dtype=np.uint64)
+    outs, op = _unpack_outs(caps)
+    ol = np.zeros(max(1, count), dtype=np.uint64)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    failed = C.c_uint32(0)
+    ip = (C.c_void_p * max(1, count))(*[c.ctypes.data if c.size else None for c in cts])
+    check(_lib.lib().vds_ec_block_unpack_host_batch(
+        count, ip, ln.ctypes.data_as(_lib.u64p), kk.ctypes.data if count else None, ii.ctypes.data if count else None,
+        op, cp.ctypes.data_as(_lib.u64p), ol.ctypes.data_as(_lib.u64p), st.ctypes.data_as(_lib.i32p),
+        C.byref(failed)), "block_unpack_host_batch")
+    return [(None if st[o] else outs[o][:int(ol[o])].tobytes(), int(st[o])) for o in range(count)]
+
+
 def block_pack_batch(datas: Sequence, level: int = 6) -> list:
     """save_block / client::save for a batch of blocks: per block (id, key,
     crypted) with id = SHA-256(data), key = SHA-256(AES(id, data)) and crypted

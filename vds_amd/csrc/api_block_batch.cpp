@@ -4,10 +4,12 @@
 // reference's client::save for a batch of blocks as four launches
 // (vds_ec_block_pack_batch_device: id = SHA-256(data), key =
 // SHA-256(AES(id, data)), crypted = AES(key, deflate(data));
-// dht_network_client.cpp:1107-1140, vds_ws.js:151-161), and the host forms
-// through pinned staging (vds_ec_block_pack_host_batch,
-// vds_ec_aes256_cbc_decrypt_host_batch).  Deflate and inflate stay the
-// caller's.
+// dht_network_client.cpp:1107-1140, vds_ws.js:151-161), client::restore the
+// same way as three (vds_ec_block_unpack_batch_device: decrypt, inflate --
+// inflate.hip through api_inflate_batch.cpp -- and the gated name check;
+// dht_network_client.cpp:1297-1316), and the host forms through pinned staging
+// (vds_ec_block_pack_host_batch, vds_ec_aes256_cbc_decrypt_host_batch,
+// vds_ec_block_unpack_host_batch).  Deflate stays the caller's.
 // (api_internal.hpp lists the host runtime's translation units.)
 #include "api_internal.hpp"
 
@@ -238,7 +240,175 @@ int enqueue_pack(uint32_t count, const uint8_t *const *datas, const uint64_t *da
   return rc;
 }
 
+int check_unpack_args(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                      const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs, const uint64_t *out_caps,
+                      const void *out_lens, const void *statuses, bool device, uint64_t *ntiles) {
+  int rc = check_inflate_args(count, crypted, crypted_lens, outs, out_caps);
+  if (rc) return rc;
+  *ntiles = 0;
+  if (count == 0) return VDS_EC_OK;
+  if (!keys || !ids || !out_lens || !statuses) return VDS_EC_EINVAL;
+  if (device && ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_lens) |
+                  reinterpret_cast<uintptr_t>(statuses)) & 3u))
+    return VDS_EC_EINVAL;
+  for (uint32_t o = 0; o < count; ++o) *ntiles += dec_tiles(crypted_lens[o]);
+  return *ntiles > 0x7FFFFFFFull ? VDS_EC_EINVAL : VDS_EC_OK;  // (the decrypt launch's workgroups)
+}
+
+// client::restore for a batch: decrypt into the pack's scratch (the
+// plaintexts at 16-byte aligned offsets, then a length and a status a block),
+// inflate from there under those lengths and statuses, name check under the
+// inflate's.  The scratch's last reader is the inflate.  (Validated; the
+// device is ready.)
+int enqueue_unpack(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens, const uint8_t *keys,
+                   const uint8_t *ids, uint8_t *const *outs, const uint64_t *out_caps, uint32_t *out_lens,
+                   int32_t *statuses, uint64_t ntiles, hipStream_t s) {
+  PackScratch *ps = pack_scratch();
+  if (!ps) return VDS_EC_ENODEV;
+  uint64_t plain_b = 0;
+  for (uint32_t o = 0; o < count; ++o) plain_b += (crypted_lens[o] + 15) & ~15ull;
+  const uint64_t need = plain_b + 8ull * count;
+  std::lock_guard<std::mutex> g(ps->mu);
+  if (!ps->done && hipEventCreateWithFlags(&ps->done, hipEventDisableTiming) != hipSuccess) return VDS_EC_ENODEV;
+  if (need > ps->cap) {
+    if (ps->pending) (void)hipEventSynchronize(ps->done);
+    ps->pending = false;
+    if (ps->d) (void)hipFree(ps->d);
+    ps->d = nullptr;
+    ps->cap = 0;
+    size_t cap = 1u << 20;
+    while (cap < need) cap *= 2;
+    if (hipMalloc(&ps->d, cap) != hipSuccess) return VDS_EC_ENOMEM;
+    ps->cap = cap;
+  }
+  if (ps->pending) {
+    const hipError_t e = hipStreamWaitEvent(s, ps->done, 0);
+    if (e != hipSuccess) return hip_status(e);
+  }
+  PackTables &t = pack_tables();
+  t.tmp.resize(count);
+  uint64_t at = 0;
+  for (uint32_t o = 0; o < count; ++o) {
+    t.tmp[o] = ps->d + at;
+    at += (crypted_lens[o] + 15) & ~15ull;
+  }
+  uint32_t *plain_lens = reinterpret_cast<uint32_t *>(ps->d + plain_b);
+  int32_t *plain_st = reinterpret_cast<int32_t *>(ps->d + plain_b + 4ull * count);
+  int rc = enqueue_decrypt(count, crypted, crypted_lens, keys, nullptr, t.tmp.data(), plain_lens, plain_st, ntiles, s);
+  if (!rc)
+    rc = enqueue_inflate(count, t.tmp.data(), crypted_lens, outs, out_caps, out_lens, statuses, plain_lens, plain_st, s);
+  // (the scratch's last reader, also when a step failed behind an earlier one's launch)
+  ps->pending = hipEventRecord(ps->done, s) == hipSuccess;
+  if (!ps->pending) (void)hipStreamSynchronize(s);
+  if (!rc) rc = sha256_gated_batch_device(count, outs, out_caps, ids, out_lens, statuses, s);
+  return rc;
+}
+
 }  // namespace
+
+int block_unpack_batch_device(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                              const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs, const uint64_t *out_caps,
+                              uint32_t *out_lens, int32_t *statuses, hipStream_t s) {
+  uint64_t ntiles = 0;
+  int rc = check_unpack_args(count, crypted, crypted_lens, keys, ids, outs, out_caps, out_lens, statuses, true, &ntiles);
+  if (rc || count == 0) return rc;
+  if ((rc = device_ready())) return rc;
+  return enqueue_unpack(count, crypted, crypted_lens, keys, ids, outs, out_caps, out_lens, statuses, ntiles, s);
+}
+
+int block_unpack_host_batch(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                            const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs, const uint64_t *out_caps,
+                            uint64_t *out_lens, int32_t *statuses, uint32_t *failed) {
+  uint64_t all_tiles = 0;
+  int rc = check_unpack_args(count, crypted, crypted_lens, keys, ids, outs, out_caps, out_lens, statuses, false,
+                             &all_tiles);
+  if (rc) return rc;
+  if (failed) *failed = 0;
+  if (count == 0) return VDS_EC_OK;
+  if ((rc = device_ready())) return rc;
+  SaveTempStage *st = save_temp_stage();
+  if (!st) return VDS_EC_ENODEV;
+  std::vector<uint64_t> c_off, o_off;
+  std::vector<const uint8_t *> d_crypted;
+  std::vector<uint8_t *> d_outs;
+  std::vector<Copy> parts;
+  uint32_t bad = 0;
+  for (uint32_t o0 = 0; o0 < count;) {
+    // The group: blocks o0 .. o1-1, at most 64 MiB each way.  Ciphertexts at
+    // 16-byte aligned offsets of the input staging, then the keys and the ids;
+    // in the output staging the outputs' capacities at 16-byte aligned
+    // offsets, then the lengths and the statuses.
+    c_off.clear();
+    o_off.clear();
+    uint64_t ct_b = 0, out_b = 0, ntiles = 0;
+    uint32_t o1 = o0;
+    while (o1 < count && o1 - o0 < kSaveTempGroupObjects) {
+      const uint64_t ca = (ct_b + 15) & ~15ull, oa = (out_b + 15) & ~15ull;
+      if (o1 > o0 && (ca + crypted_lens[o1] > kSaveTempGroupBytes || oa + out_caps[o1] > kSaveTempGroupBytes)) break;
+      c_off.push_back(ca);
+      o_off.push_back(oa);
+      ct_b = ca + crypted_lens[o1];
+      out_b = oa + out_caps[o1];
+      ntiles += dec_tiles(crypted_lens[o1]);
+      ++o1;
+    }
+    const uint32_t cnt = o1 - o0;
+    const uint64_t key_off = (ct_b + 15) & ~15ull, id_off = key_off + 32ull * cnt, in_b = id_off + 32ull * cnt;
+    const uint64_t len_off = (out_b + 15) & ~15ull, st_off = len_off + 4ull * cnt, back_b = st_off + 4ull * cnt;
+    if ((rc = st->reserve(in_b, back_b))) return rc;
+    parts.clear();
+    for (uint32_t j = 0; j < cnt; ++j) parts.push_back({st->h_in + c_off[j], crypted[o0 + j], crypted_lens[o0 + j]});
+    parts.push_back({st->h_in + key_off, keys + 32ull * o0, 32ull * cnt});
+    parts.push_back({st->h_in + id_off, ids + 32ull * o0, 32ull * cnt});
+    parallel_copy(parts);
+    hipError_t e = hipMemcpyAsync(st->d_in, st->h_in, in_b, hipMemcpyHostToDevice, st->stream);
+    if (e != hipSuccess) return hip_status(e);
+    auto drained = [&](int r) {
+      (void)hipStreamSynchronize(st->stream);
+      return r;
+    };
+    d_crypted.resize(cnt);
+    d_outs.resize(cnt);
+    for (uint32_t j = 0; j < cnt; ++j) {
+      d_crypted[j] = st->d_in + c_off[j];
+      d_outs[j] = st->d_out + o_off[j];
+    }
+    rc = enqueue_unpack(cnt, d_crypted.data(), crypted_lens + o0, st->d_in + key_off, st->d_in + id_off, d_outs.data(),
+                        out_caps + o0, reinterpret_cast<uint32_t *>(st->d_out + len_off),
+                        reinterpret_cast<int32_t *>(st->d_out + st_off), ntiles, st->stream);
+    if (rc) return drained(rc);
+    // lengths and statuses first: only what was unpacked comes back
+    e = hipMemcpyAsync(st->h_out + len_off, st->d_out + len_off, back_b - len_off, hipMemcpyDeviceToHost, st->stream);
+    if (e != hipSuccess) return drained(hip_status(e));
+    if ((rc = hip_status(hipStreamSynchronize(st->stream)))) return rc;
+    const uint32_t *dl = reinterpret_cast<const uint32_t *>(st->h_out + len_off);
+    const int32_t *ds = reinterpret_cast<const int32_t *>(st->h_out + st_off);
+    uint64_t hi = 0;
+    for (uint32_t j = 0; j < cnt; ++j)
+      if (ds[j] == VDS_EC_OK) hi = std::max<uint64_t>(hi, o_off[j] + dl[j]);
+    if (hi) {
+      e = hipMemcpyAsync(st->h_out, st->d_out, hi, hipMemcpyDeviceToHost, st->stream);
+      if (e != hipSuccess) return drained(hip_status(e));
+      if ((rc = hip_status(hipStreamSynchronize(st->stream)))) return rc;
+    }
+    // a block whose status is non-zero has nothing scattered
+    parts.clear();
+    for (uint32_t j = 0; j < cnt; ++j) {
+      const uint32_t o = o0 + j;
+      statuses[o] = ds[j];
+      out_lens[o] = ds[j] ? 0 : dl[j];
+      if (ds[j]) {
+        ++bad;
+        continue;
+      }
+      parts.push_back({outs[o], st->h_out + o_off[j], dl[j]});
+    }
+    parallel_copy(parts);
+    o0 = o1;
+  }
+  if (failed) *failed = bad;
+  return VDS_EC_OK;
+}
 
 int aes_encrypt_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, const uint8_t *keys,
                              const uint8_t *ivs, uint8_t *const *outs, hipStream_t s) {
@@ -483,6 +653,20 @@ int vds_ec_aes256_cbc_decrypt_host_batch(uint32_t count, const uint8_t *const *i
                                          const uint8_t *keys, const uint8_t *ivs, uint8_t *const *outs,
                                          uint64_t *out_lens, int32_t *statuses, uint32_t *failed) {
   return vds_ec::api::aes_decrypt_host_batch(count, ins, lens, keys, ivs, outs, out_lens, statuses, failed);
+}
+
+int vds_ec_block_unpack_batch_device(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                                     const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs,
+                                     const uint64_t *out_caps, uint32_t *out_lens, int32_t *statuses, void *stream) {
+  return vds_ec::api::block_unpack_batch_device(count, crypted, crypted_lens, keys, ids, outs, out_caps, out_lens,
+                                                statuses, vds_ec::api::as_stream(stream));
+}
+
+int vds_ec_block_unpack_host_batch(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
+                                   const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs,
+                                   const uint64_t *out_caps, uint64_t *out_lens, int32_t *statuses, uint32_t *failed) {
+  return vds_ec::api::block_unpack_host_batch(count, crypted, crypted_lens, keys, ids, outs, out_caps, out_lens,
+                                              statuses, failed);
 }
 
 }  // extern "C"

@@ -22,8 +22,10 @@
 //   api_dgram_batch.cpp  the node-to-node datagram layer: batched HMAC-SHA256,
 //                       sealing and opening of datagrams (device and host);
 //   api_block_batch.cpp  file blocks: batched AES-256-CBC, the pack of a batch
-//                       of blocks (hash, encrypt, hash, encrypt) and the host
-//                       forms of both;
+//                       of blocks (hash, encrypt, hash, encrypt), the unpack
+//                       (decrypt, inflate, name check) and the host forms;
+//   api_inflate_batch.cpp  zlib streams of a batch inflated on the device, and
+//                       the host form;
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -214,6 +216,20 @@ int save_temp_host_batch(uint32_t k, uint32_t n, uint32_t count, const uint8_t *
                          uint32_t *replica_sizes);
 int sha256_check_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
                               const uint8_t *expected, uint8_t *digests, uint8_t *verdicts, hipStream_t s);
+// The unpack chain's name check (k_sha256_batch<true, true>): message j, whose
+// length and status exist only on the device (lens_dev[j] <= caps[j], statuses
+// [j]), hashed and compared with expected + 32 j where its status lets it.
+// The caller has validated the arguments and found the device.
+int sha256_gated_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *caps,
+                              const uint8_t *expected, uint32_t *lens_dev, int32_t *statuses, hipStream_t s);
+// zlib streams inflated (api_inflate_batch.cpp, inflate.hip).  enqueue_inflate:
+// validated arguments, the device ready; in_lens / gate: the unpack chain's
+// device arrays (InflateLaunch), or null.
+int check_inflate_args(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, uint8_t *const *outs,
+                       const uint64_t *out_caps);
+int enqueue_inflate(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, uint8_t *const *outs,
+                    const uint64_t *out_caps, uint32_t *out_lens, int32_t *statuses, const uint32_t *in_lens,
+                    const int32_t *gate, hipStream_t s);
 int repair_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
                         const uint64_t *chunk_sizes, uint32_t nt, const uint16_t *targets, uint8_t *const *outs,
                         uint8_t *digests, const uint8_t *expected, uint8_t *verdicts, hipStream_t s);

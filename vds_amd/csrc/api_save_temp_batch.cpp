@@ -28,12 +28,17 @@ struct ShaBatchScratch {
   // check mode (k_sha256_batch<true>): checks[g] beside groups[g]
   bool check = false;
   std::vector<ShaBatchCheck> checks;
-  void clear(bool check_mode = false) {
+  // gated mode (k_sha256_batch<true, true>): gates[g] beside groups[g] and checks[g]
+  bool gated = false;
+  std::vector<ShaBatchGate> gates;
+  void clear(bool check_mode = false, bool gated_mode = false) {
     groups.clear();
     m.clear();
     ptrs.clear();
     checks.clear();
+    gates.clear();
     check = check_mode;
+    gated = gated_mode;
   }
   void add(uint64_t msg, uint64_t pitch, uint64_t len, uint8_t *digests, uint32_t cnt,
            const uint8_t *expected = nullptr, uint8_t *verdicts = nullptr) {
@@ -114,7 +119,8 @@ int launch_sha_groups(ShaBatchScratch &sc, hipStream_t s) {
   const size_t o_wave = o_spans + ng * sizeof(ShaBatchSpan);
   const size_t o_ptrs = (o_wave + (waves + 1) * sizeof(uint32_t) + 7) & ~size_t(7);
   const size_t o_checks = o_ptrs + sc.ptrs.size() * sizeof(uint8_t *);  // (check mode: after the pointer tables)
-  const size_t bytes = o_checks + (sc.check ? ng * sizeof(ShaBatchCheck) : 0);
+  const size_t o_gates = o_checks + (sc.check ? ng * sizeof(ShaBatchCheck) : 0);  // (gated mode: after the checks)
+  const size_t bytes = o_gates + (sc.gated ? ng * sizeof(ShaBatchGate) : 0);
   ParamSlot *slot = nullptr;
   hipError_t e = param_acquire_n(1, &bytes, &slot);
   if (e != hipSuccess) return hip_status(e);
@@ -122,6 +128,7 @@ int launch_sha_groups(ShaBatchScratch &sc, hipStream_t s) {
   ShaBatchSpan *spans = reinterpret_cast<ShaBatchSpan *>(slot->h + o_spans);
   uint32_t *wave_group = reinterpret_cast<uint32_t *>(slot->h + o_wave);
   ShaBatchCheck *checks = reinterpret_cast<ShaBatchCheck *>(slot->h + o_checks);
+  ShaBatchGate *gates = reinterpret_cast<ShaBatchGate *>(slot->h + o_gates);
   uint64_t lane = 0;
   for (size_t i = 0; i < ng; ++i) {
     const uint32_t g = sc.order[i];
@@ -129,6 +136,7 @@ int launch_sha_groups(ShaBatchScratch &sc, hipStream_t s) {
     if (d.pitch == kShaBatchPtrTable) d.msg += reinterpret_cast<uintptr_t>(slot->d + o_ptrs);
     groups[i] = d;
     if (sc.check) checks[i] = sc.checks[g];
+    if (sc.gated) gates[i] = sc.gates[g];
     const uint32_t m = sc.m[g];
     if (m % 64 == 0) lane = (lane + 63) & ~63ull;
     spans[i] = ShaBatchSpan{(uint32_t)lane, m};
@@ -147,7 +155,12 @@ int launch_sha_groups(ShaBatchScratch &sc, hipStream_t s) {
     b.spans = reinterpret_cast<const ShaBatchSpan *>(slot->d + o_spans);
     b.wave_group = reinterpret_cast<const uint32_t *>(slot->d + o_wave);
     b.waves = (uint32_t)waves;
-    if (sc.check)
+    if (sc.gated)
+      e = launch_sha256_gated_batch(
+          ShaBatchGatedLaunch{ShaBatchCheckLaunch{b, reinterpret_cast<const ShaBatchCheck *>(slot->d + o_checks)},
+                              reinterpret_cast<const ShaBatchGate *>(slot->d + o_gates)},
+          s);
+    else if (sc.check)
       e = launch_sha256_check_batch(
           ShaBatchCheckLaunch{b, reinterpret_cast<const ShaBatchCheck *>(slot->d + o_checks)}, s);
     else
@@ -338,6 +351,18 @@ int sha256_check_batch_device(uint32_t count, const uint8_t *const *msgs, const 
   for (uint32_t j = 0; j < count; ++j)
     sc.add(reinterpret_cast<uintptr_t>(msgs[j]), 0, lens[j], digests ? digests + 32ull * j : nullptr, 1,
            expected + 32ull * j, verdicts + j);
+  return launch_sha_groups(sc, s);
+}
+
+int sha256_gated_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *caps,
+                              const uint8_t *expected, uint32_t *lens_dev, int32_t *statuses, hipStream_t s) {
+  ShaBatchScratch &sc = sha_batch_scratch();
+  sc.clear(true, true);
+  for (uint32_t j = 0; j < count; ++j) {
+    // (ordered by the capacity, the length's upper bound: the length itself is on the device)
+    sc.add(reinterpret_cast<uintptr_t>(msgs[j]), 0, caps[j], nullptr, 1, expected + 32ull * j, nullptr);
+    sc.gates.push_back(ShaBatchGate{reinterpret_cast<uintptr_t>(lens_dev + j), reinterpret_cast<uintptr_t>(statuses + j)});
+  }
   return launch_sha_groups(sc, s);
 }
 

@@ -214,6 +214,40 @@ struct AesDecLaunch {
   uint64_t keys, ivs;          // as above, by message index
   uint64_t out_lens, statuses;  // uint32_t / int32_t a message
 };
+// Gated mode (k_sha256_batch<true, true>: the unpack chain's name check, whose
+// lengths and statuses exist only on the device): gates[g] beside groups[g] and
+// checks[g], every group one message.  The lane reads the message's status; if
+// it is neither VDS_EC_OK nor VDS_EC_EINFLATE_SHORT it zeroes the length and
+// does nothing else.  Else it hashes min(*len, ShaBatchGroup::len) bytes (the
+// host planned with the upper bound), compares with the expected bytes, and
+// writes VDS_EC_OK, or VDS_EC_ECORRUPT and a length of 0.  No verdict byte.
+struct ShaBatchGate {
+  uint64_t len;     // its uint32_t length, 4-byte aligned
+  uint64_t status;  // its int32_t status, 4-byte aligned
+};
+struct ShaBatchGatedLaunch {
+  ShaBatchCheckLaunch c;
+  const ShaBatchGate *gates;
+};
+// zlib streams inflated (inflate.hip): one wave per stream, the streams longest
+// input first; msgs[w] is wave w's.
+struct InflateMsg {
+  uint64_t in;   // len bytes, any alignment; never dereferenced when len == 0
+  uint64_t out;  // cap bytes, any alignment, not overlapping in
+  uint32_t len;
+  uint32_t cap;
+  uint32_t idx;  // the message's place in the caller's order
+  uint32_t reserved;
+};
+struct InflateLaunch {
+  const InflateMsg *msgs;
+  uint32_t count;
+  uint64_t out_lens, statuses;  // uint32_t / int32_t a message, by idx
+  // The unpack chain (0: not given): message idx's input length is
+  // min(in_lens[idx], len), and a message whose gate[idx] is not VDS_EC_OK
+  // gets that status, out_len 0 and no other work.
+  uint64_t in_lens, gate;
+};
 // The "upload" answer of one message as a websocket frame (base64.hip,
 // k_ws_upload_answer_batch: one wave a message).  The few bytes that vary in
 // length come from the host: head = the frame header and {"id":"<id>","result":
@@ -562,6 +596,9 @@ hipError_t launch_b64_encode_gated_batch(const B64EncMsg *msgs, const B64EncGate
 hipError_t launch_aes_encrypt_batch(const AesEncMsg *msgs, uint32_t count, const uint8_t *keys, const uint8_t *ivs,
                                     hipStream_t s, bool lane_chain = false);
 hipError_t launch_aes_decrypt_batch(const AesDecLaunch &l, hipStream_t s);
+// The gated name check of the unpack chain (sha256.hip), and the inflate of a batch (inflate.hip).
+hipError_t launch_sha256_gated_batch(const ShaBatchGatedLaunch &g, hipStream_t s);
+hipError_t launch_inflate_batch(const InflateLaunch &l, hipStream_t s);
 // One message on the calling CPU thread (aes_host.cpp); the decrypt returns its status.
 void aes256_cbc_encrypt_host(const uint8_t key[32], const uint8_t iv[16], const uint8_t *in, uint64_t len,
                              uint8_t *out);

@@ -16,6 +16,7 @@
 
 #include <type_traits>
 
+#include "../../include/vds_ec.h"
 #include "ec_internal.hpp"
 #include "sha256_device.hpp"
 
@@ -123,6 +124,9 @@ __global__ __launch_bounds__(64) void k_sha256(const uint8_t *base, uint64_t len
 // (the batch kernel's tables, whichever launch struct its instance takes)
 __device__ __forceinline__ const ShaBatchLaunch &tables(const ShaBatchLaunch &l) { return l; }
 __device__ __forceinline__ const ShaBatchLaunch &tables(const ShaBatchCheckLaunch &l) { return l.b; }
+__device__ __forceinline__ const ShaBatchLaunch &tables(const ShaBatchGatedLaunch &l) { return l.c.b; }
+__device__ __forceinline__ const ShaBatchCheck *checks_of(const ShaBatchCheckLaunch &l) { return l.checks; }
+__device__ __forceinline__ const ShaBatchCheck *checks_of(const ShaBatchGatedLaunch &l) { return l.c.checks; }
 
 // Messages of different lengths, one lane each: lane j finds its group between
 // its wave's two wave_group entries (ShaBatchLaunch, ec_internal.hpp), then
@@ -139,9 +143,15 @@ __device__ __forceinline__ const ShaBatchLaunch &tables(const ShaBatchCheckLaunc
 // lane also compares its digest with its group's expected bytes and writes a
 // verdict byte (ShaBatchCheck, ec_internal.hpp); the expected bytes are read
 // as the message is, from the aligned dwords holding at least one of them.
-template <bool CHECK>
+//
+// GATED (the unpack chain's name check, every group one message): the length
+// and a status come from device arrays (ShaBatchGate, ec_internal.hpp); the
+// lane hashes only where the status lets it and writes the final status, and
+// a length of 0 where that is not VDS_EC_OK.
+template <bool CHECK, bool GATED = false>
 __global__ __launch_bounds__(64) void k_sha256_batch(
-    std::conditional_t<CHECK, ShaBatchCheckLaunch, ShaBatchLaunch> launch) {
+    std::conditional_t<GATED, ShaBatchGatedLaunch, std::conditional_t<CHECK, ShaBatchCheckLaunch, ShaBatchLaunch>>
+        launch) {
   const ShaBatchLaunch &b = tables(launch);
   const uint32_t wv = blockIdx.x;
   const uint32_t j = wv * 64u + threadIdx.x;
@@ -157,7 +167,16 @@ __global__ __launch_bounds__(64) void k_sha256_batch(
   const uint32_t idx = j - sp.first;
   if (idx >= sp.m) return;  // a lane between two groups, or past the last one
   const ShaBatchGroup g = b.groups[lo];
-  const uint64_t len = g.len;
+  uint64_t len = g.len;
+  if constexpr (GATED) {
+    const ShaBatchGate gt = launch.gates[lo];
+    const int32_t st = *reinterpret_cast<const __attribute__((address_space(1))) int32_t *>(gt.status);
+    if (st != VDS_EC_OK && st != VDS_EC_EINFLATE_SHORT) {
+      *reinterpret_cast<__attribute__((address_space(1))) uint32_t *>(gt.len) = 0u;
+      return;
+    }
+    len = min(len, (uint64_t)*reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(gt.len));
+  }
   // (the addresses come from the tables as integers: global pointers made
   // from them keep the loads and stores global_* rather than flat_*)
   typedef const __attribute__((address_space(1))) uint64_t *gptr_u64;
@@ -233,7 +252,7 @@ __global__ __launch_bounds__(64) void k_sha256_batch(
       for (int t = 0; t < 4; ++t) dg[4 * i + t] = (uint8_t)(h[i] >> (24 - 8 * t));
   }
   if constexpr (CHECK) {
-    const ShaBatchCheck c = launch.checks[lo];
+    const ShaBatchCheck c = checks_of(launch)[lo];
     if (c.expected == 0) return;
     // expected byte 4i..4i+3 big-endian = word i of the digest: dwords 0..7 of
     // ep hold expected bytes whatever esh is, dword 8 only when esh != 0
@@ -248,9 +267,16 @@ __global__ __launch_bounds__(64) void k_sha256_batch(
     uint32_t diff = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) diff |= h[i] ^ __builtin_amdgcn_perm(raw[i + 1], raw[i], esel);
-    reinterpret_cast<gptr_u8>(c.verdicts)[idx] = diff ? 1 : 0;
+    if constexpr (GATED) {
+      const ShaBatchGate gt = launch.gates[lo];
+      *reinterpret_cast<__attribute__((address_space(1))) int32_t *>(gt.status) = diff ? VDS_EC_ECORRUPT : VDS_EC_OK;
+      if (diff) *reinterpret_cast<__attribute__((address_space(1))) uint32_t *>(gt.len) = 0u;
+    } else {
+      reinterpret_cast<gptr_u8>(c.verdicts)[idx] = diff ? 1 : 0;
+    }
   }
 }
+
 
 }  // namespace
 
@@ -263,6 +289,12 @@ hipError_t launch_sha256_batch(const ShaBatchLaunch &b, hipStream_t s) {
 hipError_t launch_sha256_check_batch(const ShaBatchCheckLaunch &c, hipStream_t s) {
   if (c.b.waves == 0) return hipSuccess;
   hipLaunchKernelGGL(k_sha256_batch<true>, dim3(c.b.waves), dim3(64), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_sha256_gated_batch(const ShaBatchGatedLaunch &g, hipStream_t s) {
+  if (g.c.b.waves == 0) return hipSuccess;
+  hipLaunchKernelGGL((k_sha256_batch<true, true>), dim3(g.c.b.waves), dim3(64), 0, s, g);
   return hipGetLastError();
 }
 

@@ -15,7 +15,7 @@ using namespace vds_ec::api;
 namespace vds_ec {
 namespace api {
 
-constexpr int kVersion = 101;  // 0.1.1: file blocks (AES-256-CBC, vds_ec_block_pack_*)
+constexpr int kVersion = 102;  // 0.1.2: file blocks unpacked (vds_ec_inflate_*, vds_ec_block_unpack_*)
 
 
 int hip_status(hipError_t e) {
@@ -1024,6 +1024,9 @@ const char *vds_ec_strerror(int status) {
     case VDS_EC_EWS_PING: return "websocket ping";
     case VDS_EC_ECRYPT_LENGTH: return "EVP_CipherFinal_ex failed (wrong final block length)";
     case VDS_EC_ECRYPT_PADDING: return "EVP_CipherFinal_ex failed (bad decrypt)";
+    case VDS_EC_EINFLATE_DATA: return "inflate failed";
+    case VDS_EC_EINFLATE_SHORT: return "inflate: the input ends before the stream does";
+    case VDS_EC_EINFLATE_SPACE: return "inflate: the output's capacity is too small";
     default: return "unknown vds_ec status";
   }
 }
