@@ -1028,7 +1028,10 @@ int vds_ec_aes256_cbc_decrypt_host_batch(uint32_t count, const uint8_t *const *i
  *                          error shows only once the bits that reveal it are
  *                          inside the input.  An input of length 0 is SHORT.
  *   VDS_EC_EINFLATE_SPACE  the next literal, match or stored run would pass
- *                          out_cap.  out_len 0, contents unspecified.
+ *                          out_cap.  out_len 0, contents unspecified.  As in
+ *                          zlib, a full output comes before the match's own
+ *                          error: a distance reaching before the output's
+ *                          start is SPACE where out_cap bytes are out already.
  * No byte is written at or past out + out_cap, whatever the stream says.
  *
  * vds_ec_inflate_host: ONE message on the calling thread, no GPU, no zlib.

@@ -27,6 +27,33 @@ def expected(stream: bytes):
     return (OK if d.eof else EINFLATE_SHORT), out
 
 
+def expected_cap(stream: bytes, cap: int):
+    """(status, bytes) under a finite capacity cap >= 1, from zlib alone.  What zlib makes of the stream
+    with room for cap bytes: an error it meets is DATA, its end is OK, fewer than cap bytes are SHORT with
+    them.  With cap bytes delivered and no end, a fresh object with room for cap + 1 tells whether a byte
+    more was wanted (SPACE: it comes, or zlib meets an error behind it) or the bytes fitted exactly.  (A
+    second call on the first object would not do: zlib runs on to a trailer's error inside one call.)
+    max_length = 0 means unlimited in Python, so cap = 0 has no answer here."""
+    assert cap >= 1
+    d = zlib.decompressobj()
+    try:
+        out = d.decompress(stream, cap)
+    except zlib.error:
+        return EINFLATE_DATA, b""
+    if d.eof:
+        return OK, out
+    if len(out) < cap:
+        return EINFLATE_SHORT, out
+    d = zlib.decompressobj()
+    try:
+        more = d.decompress(stream, cap + 1)
+    except zlib.error:
+        return EINFLATE_SPACE, b""
+    if len(more) == cap + 1:
+        return EINFLATE_SPACE, b""
+    return (OK if d.eof else EINFLATE_SHORT), more
+
+
 _WORDS = None
 
 

@@ -4,6 +4,7 @@ and _host_batch): decrypt, inflate, name check, no host step between them.
 The checkers: Python's zlib and hashlib, and the library's host cipher
 (pinned against OpenSSL's recorded answers by tests/test_aes_host_cpu.py).
 Bit-exact, status for status."""
+import collections
 import ctypes as C
 import hashlib
 import zlib
@@ -135,6 +136,31 @@ def test_one_block_per_failure(gpu, vds_lib, packed):
     want = [_reference(vds_lib, c, k, i, cap) for c, k, i, cap, _ in batch]
     assert [w[0] for w in want] == [b[4] for b in batch]  # each is the failure it is meant to be
     assert _device_unpack(torch, [b[:4] for b in batch]) == want
+
+
+def test_forms_no_compressor_emits(gpu, vds_lib):
+    """64 streams of tests/inflate_forms.py -- table shapes up to 15 bits, degenerate sets, refused headers,
+    truncated streams -- as block bodies: the inflate reached through the decrypt's gate and lengths, the
+    bytes behind each message PKCS#7 padding.  A stream that ends short goes on to the hash."""
+    import torch
+    import inflate_forms as F
+    iv = A.block_iv()
+    sha = lambda b: hashlib.sha256(b).digest()
+    shapes = F.table_shapes()
+    cases = F.degenerate() + shapes[:14] + shapes[14::11][:30]
+    short = [c for c in F.prefixes() if c[3] == K.EINFLATE_SHORT and len(c[4]) > 10][::97][:6]
+    assert len(short) == 6
+    blocks, want = [], []
+    for i, (name, s, cap, st, out) in enumerate((cases + short)[:64]):
+        key = K.splitmix(32, 900 + i)
+        named = i % 2 == 0  # of the short ones: the id names what was delivered, or something else
+        ident = sha(out) if st == 0 or (st == K.EINFLATE_SHORT and named) else sha(b"not this")
+        blocks.append((A.host_encrypt(vds_lib, key, iv, s), key, ident, cap))
+        want.append((K.EINFLATE_DATA, b"") if st == K.EINFLATE_DATA else (0, out) if st == 0 or named else (K.ECORRUPT, b""))
+    assert len(blocks) == 64 and len({len(b[0]) - len(c[1]) for b, c in zip(blocks, cases + short)}) >= 8
+    assert [_reference(vds_lib, *b) for b in blocks] == want
+    assert collections.Counter(w[0] for w in want) == {0: 53, K.EINFLATE_DATA: 8, K.ECORRUPT: 3}
+    assert _device_unpack(torch, blocks) == want
 
 
 def test_host_form_leaves_failed_outputs_untouched(gpu, vds_lib, packed):

@@ -388,7 +388,9 @@ struct Wave {
         drop(nb);
         const uint32_t D = dbase + peek(x);
         drop(x);
-        if (D > pos + nlit) return VDS_EC_EINFLATE_DATA;  // "invalid distance too far back": an error, not a read
+        // "invalid distance too far back": an error, not a read -- which zlib looks for only once the
+        // match's first byte has room
+        if (D > pos + nlit) return pos + nlit >= cap ? VDS_EC_EINFLATE_SPACE : VDS_EC_EINFLATE_DATA;
         if ((uint64_t)pos + nlit + L > cap) return VDS_EC_EINFLATE_SPACE;
         flush();
         copy_match(D, L);

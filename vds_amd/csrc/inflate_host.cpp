@@ -254,7 +254,8 @@ int inflate(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_
       b.drop(nb);
       const uint32_t D = dbase + b.peek(x);
       b.drop(x);
-      if (D > pos) return stop(VDS_EC_EINFLATE_DATA);  // "invalid distance too far back"
+      // "invalid distance too far back" -- which zlib looks for only once the match's first byte has room
+      if (D > pos) return stop(pos >= cap ? VDS_EC_EINFLATE_SPACE : VDS_EC_EINFLATE_DATA);
       if (pos + L > cap) return stop(VDS_EC_EINFLATE_SPACE);
       for (uint32_t i = 0; i < L; ++i) out[pos + i] = out[pos + i - D];
       pos += L;
