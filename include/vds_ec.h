@@ -933,9 +933,12 @@ int vds_ec_ws_download16_host_batch(uint16_t k, uint32_t count, const int32_t *i
  *     key     = SHA-256(AES-256-CBC(id, pack_block_iv, data))
  *     crypted = AES-256-CBC(key, pack_block_iv, deflate(data))
  * and back: decrypt under key, inflate, SHA-256 == id or "Data is corrupted".
- * Deflate stays the caller's (zlib: its output differs between
- * implementations, and key does not depend on it); the way back is
- * vds_ec_block_unpack_batch_device below.  The same cipher wraps every channel
+ * The deflate is the library's own where the caller wants it
+ * (vds_ec_block_pack_deflate_batch_device below: the whole chain on the
+ * device) or the caller's (vds_ec_block_pack_batch_device takes the deflated
+ * bytes: a deflate's output differs between implementations, and key does not
+ * depend on it); the way back is vds_ec_block_unpack_batch_device below.
+ * The same cipher wraps every channel
  * message under its own key and iv (user_channel.cpp:229).
  *
  * vds_ec_aes256_cbc_padded_size: what len bytes encrypt to, (len/16 + 1) * 16.
@@ -1076,6 +1079,63 @@ int vds_ec_block_unpack_batch_device(uint32_t count, const uint8_t *const *crypt
 int vds_ec_block_unpack_host_batch(uint32_t count, const uint8_t *const *crypted, const uint64_t *crypted_lens,
                                    const uint8_t *keys, const uint8_t *ids, uint8_t *const *outs,
                                    const uint64_t *out_caps, uint64_t *out_lens, int32_t *statuses, uint32_t *failed);
+
+/* ------------------------------------------------------ file blocks: deflate
+ * The reference's deflate (kernel/vds_data/deflate.cpp) is zlib at its default
+ * level; what its inflate needs is a zlib stream that gives the data back.
+ * The library's own compressor writes one: header 78 01 (CM 8, window 32 KiB,
+ * no preset dictionary), dynamic-Huffman and stored blocks, the Adler-32.  Its
+ * bytes differ from zlib's, and they are THE SAME on the device and on the
+ * host for the same input: a body is named by its SHA-256, so two paths must
+ * not pack one block differently.  There are no per-message failures.
+ *
+ * vds_ec_deflate_bound: the size of the all-stored form,
+ * 2 + len + 5 * max(1, ceil(len / 65535)) + 4; no output is longer.
+ * vds_ec_deflate_host: ONE message on the calling thread, no GPU, no zlib.
+ * VDS_EC_EINVAL for a null out or out_len, a null in with a non-zero len, a
+ * bound >= 2^32, out_cap below the bound, input and output overlapping.     */
+uint64_t vds_ec_deflate_bound(uint64_t len);
+int vds_ec_deflate_host(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+/* `count` messages in one launch, one wave a message.  ins, lens, outs,
+ * out_caps: HOST arrays of device pointers and sizes, any alignment.
+ * out_lens: DEVICE, 4-byte aligned, every entry written by the launch.
+ * Nothing synchronises.  Everything is validated before anything is enqueued
+ * and before the device is looked for: VDS_EC_EINVAL for null arrays, a null
+ * pointer, a bound >= 2^32, out_caps[o] below the bound of lens[o],
+ * count >= 2^30, a message whose input and output overlap; count == 0 is
+ * VDS_EC_OK.  Nothing is written outside outs[o] .. outs[o] + out_caps[o].  */
+int vds_ec_deflate_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                                uint8_t *const *outs, const uint64_t *out_caps, uint32_t *out_lens, void *stream);
+/* The same on HOST pointers (out_lens host too), staged through pinned
+ * buffers in groups of at most 64 MiB each way.                             */
+int vds_ec_deflate_host_batch(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,
+                              uint8_t *const *outs, const uint64_t *out_caps, uint64_t *out_lens);
+/* vds_ec_aes256_cbc_encrypt_batch_device with the lengths on the device:
+ * message o is the first lens[o] (DEVICE, uint32, 4-byte aligned) bytes at
+ * ins[o], and lens[o] <= max_lens[o] (HOST), which orders the chains and
+ * bounds what may be read and written: padded_size(lens[o]) bytes at outs[o],
+ * never more than padded_size(max_lens[o]).  out_lens[o] (DEVICE, uint32,
+ * 4-byte aligned) receives padded_size(lens[o]).  A lens[o] above max_lens[o]
+ * is cut to it.  Validation as the encrypt's, with max_lens for lens.       */
+int vds_ec_aes256_cbc_encrypt_gated_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *max_lens,
+                                                 const uint32_t *lens, const uint8_t *keys, const uint8_t *ivs,
+                                                 uint8_t *const *outs, uint32_t *out_lens, void *stream);
+/* client::save for `count` blocks on device pointers with the deflate on the
+ * device too: five launches on the stream, no host step and no
+ * synchronisation between them -- SHA-256 of datas into ids, encrypt datas
+ * under ids into library scratch, SHA-256 of that into keys, deflate datas
+ * into library scratch, encrypt that under keys into crypted[o].
+ * crypted_caps[o] >= padded_size(deflate_bound(data_lens[o])), else
+ * VDS_EC_EINVAL; crypted_lens (DEVICE, uint32, 4-byte aligned) receives the
+ * bodies' sizes.  vds_ec_save_temp16_batch_device takes its body sizes on the
+ * host: the caller reads crypted_lens (count * 4 bytes) back before it.     */
+int vds_ec_block_pack_deflate_batch_device(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                           uint8_t *ids, uint8_t *keys, uint8_t *const *crypted,
+                                           const uint64_t *crypted_caps, uint32_t *crypted_lens, void *stream);
+/* The same on HOST pointers (ids, keys, crypted_sizes host), staged as above. */
+int vds_ec_block_pack_deflate_host_batch(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                         uint8_t *ids, uint8_t *keys, uint8_t *const *crypted,
+                                         const uint64_t *crypted_caps, uint64_t *crypted_sizes);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

@@ -187,6 +187,16 @@ SIGNATURES = {
     "vds_ec_inflate_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     "vds_ec_inflate_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vds_ec_inflate_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, u64p, i32p, u32p]),
+    "vds_ec_deflate_bound": (C.c_uint64, [C.c_uint64]),
+    "vds_ec_deflate_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
+    "vds_ec_deflate_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, C.c_void_p, C.c_void_p]),
+    "vds_ec_deflate_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, u64p]),
+    "vds_ec_aes256_cbc_encrypt_gated_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, vpp, C.c_void_p, C.c_void_p]),
+    "vds_ec_block_pack_deflate_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p,
+                                                         C.c_void_p, C.c_void_p]),
+    "vds_ec_block_pack_deflate_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p,
+                                                       u64p]),
     "vds_ec_block_unpack_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "vds_ec_block_unpack_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p, u64p,

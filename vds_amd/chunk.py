@@ -1544,6 +1544,109 @@ def block_unpack_host_batch(crypted: Sequence, keys: Sequence, ids: Sequence, ca
     return [(None if st[o] else outs[o][:int(ol[o])].tobytes(), int(st[o])) for o in range(count)]
 
 
+def deflate_bound(length: int) -> int:
+    """vds_ec_deflate_bound: the size of the all-stored form, which no output
+    of the library's deflate passes."""
+    return int(_lib.lib().vds_ec_deflate_bound(length))
+
+
+def deflate_host(data) -> bytes:
+    """vds_ec_deflate_host: one buffer into a zlib stream on the calling
+    thread, no GPU and no zlib; the bytes the device writes for the same data."""
+    d = _u8(data)
+    out = np.empty(deflate_bound(d.size), dtype=np.uint8)
+    n = C.c_uint64(0)
+    check(_lib.lib().vds_ec_deflate_host(d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size,
+                                         C.byref(n)), "deflate_host")
+    return out[:n.value].tobytes()
+
+
+def deflate_batch_device(ins, lens, outs, out_caps, out_lens, stream=None) -> None:
+    """vds_ec_deflate_batch_device: message o, lens[o] bytes at the device
+    pointer ins[o], deflated into a zlib stream at the device pointer outs[o]
+    (out_caps[o] >= deflate_bound(lens[o]) bytes); out_lens (uint32) is a
+    device buffer of one entry a message, all written by the one launch."""
+    ip, op = _ptr_table(ins), _ptr_table(outs)
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    cp = np.ascontiguousarray(np.asarray(out_caps, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ln.size == op.size == cp.size):
+        raise VdsEcError(_lib.EINVAL, "deflate_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_deflate_batch_device(
+        ln.size, ip.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p), op.ctypes.data_as(_lib.vpp),
+        cp.ctypes.data_as(_lib.u64p), _dev_ptr(out_lens), _stream_ptr(stream)), "deflate_batch_device")
+
+
+def deflate_host_batch(ins: Sequence) -> list:
+    """vds_ec_deflate_host_batch: host buffers deflated on the device in one
+    call -> one zlib stream (bytes) per buffer."""
+    ds = [_u8(d) for d in ins]
+    count = len(ds)
+    ln = np.asarray([d.size for d in ds] or [0], dtype=np.uint64)
+    outs = [np.empty(deflate_bound(d.size), dtype=np.uint8) for d in ds]
+    cp = np.asarray([o.size for o in outs] or [0], dtype=np.uint64)
+    ol = np.zeros(max(1, count), dtype=np.uint64)
+    ip = (C.c_void_p * max(1, count))(*[d.ctypes.data if d.size else None for d in ds])
+    op = (C.c_void_p * max(1, count))(*[o.ctypes.data for o in outs])
+    check(_lib.lib().vds_ec_deflate_host_batch(count, ip, ln.ctypes.data_as(_lib.u64p), op,
+                                               cp.ctypes.data_as(_lib.u64p), ol.ctypes.data_as(_lib.u64p)),
+          "deflate_host_batch")
+    return [outs[o][:int(ol[o])].tobytes() for o in range(count)]
+
+
+def aes256_cbc_encrypt_gated_batch_device(ins, max_lens, lens, keys, outs, out_lens, ivs=None, stream=None) -> None:
+    """vds_ec_aes256_cbc_encrypt_gated_batch_device: the batched encrypt with
+    the lengths on the device -- message o is the first lens[o] (device uint32)
+    bytes at ins[o], at most max_lens[o] (host); out_lens (device uint32)
+    receives aes256_cbc_padded_size(lens[o])."""
+    ip, op = _ptr_table(ins), _ptr_table(outs)
+    ml = np.ascontiguousarray(np.asarray(max_lens, dtype=np.uint64).reshape(-1))
+    if not (ip.size == ml.size == op.size):
+        raise VdsEcError(_lib.EINVAL, "aes256_cbc_encrypt_gated_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_aes256_cbc_encrypt_gated_batch_device(
+        ml.size, ip.ctypes.data_as(_lib.vpp), ml.ctypes.data_as(_lib.u64p), _dev_ptr(lens), _dev_ptr(keys),
+        _dev_ptr(ivs), op.ctypes.data_as(_lib.vpp), _dev_ptr(out_lens), _stream_ptr(stream)),
+        "aes256_cbc_encrypt_gated_batch_device")
+
+
+def block_pack_deflate_batch_device(datas, data_lens, ids, keys, crypted, crypted_caps, crypted_lens,
+                                    stream=None) -> None:
+    """vds_ec_block_pack_deflate_batch_device: client::save for a batch of
+    blocks on device pointers with the deflate on the device too -- ids + 32 o
+    = SHA-256(data o), keys + 32 o = SHA-256(AES(id, data)), crypted[o] =
+    AES(key, deflate(data o)), five launches; crypted_caps[o] >=
+    aes256_cbc_padded_size(deflate_bound(data_lens[o])), crypted_lens (device
+    uint32) receives the bodies' sizes."""
+    dp, cp = _ptr_table(datas), _ptr_table(crypted)
+    dl = np.ascontiguousarray(np.asarray(data_lens, dtype=np.uint64).reshape(-1))
+    cc = np.ascontiguousarray(np.asarray(crypted_caps, dtype=np.uint64).reshape(-1))
+    if not (dp.size == dl.size == cp.size == cc.size):
+        raise VdsEcError(_lib.EINVAL, "block_pack_deflate_batch: the arrays do not describe one batch")
+    check(_lib.lib().vds_ec_block_pack_deflate_batch_device(
+        dl.size, dp.ctypes.data_as(_lib.vpp), dl.ctypes.data_as(_lib.u64p), _dev_ptr(ids), _dev_ptr(keys),
+        cp.ctypes.data_as(_lib.vpp), cc.ctypes.data_as(_lib.u64p), _dev_ptr(crypted_lens), _stream_ptr(stream)),
+        "block_pack_deflate_batch_device")
+
+
+def block_pack_deflate_host_batch(datas: Sequence) -> list:
+    """vds_ec_block_pack_deflate_host_batch: one (id, key, crypted) per block
+    (host bytes), every step on the device: crypted = AES(key,
+    deflate_host(data))."""
+    ds = [_u8(d) for d in datas]
+    count = len(ds)
+    dl = np.asarray([d.size for d in ds] or [0], dtype=np.uint64)
+    outs = [np.empty(aes256_cbc_padded_size(deflate_bound(d.size)), dtype=np.uint8) for d in ds]
+    cc = np.asarray([o.size for o in outs] or [0], dtype=np.uint64)
+    ids = np.empty((max(1, count), 32), dtype=np.uint8)
+    keys = np.empty((max(1, count), 32), dtype=np.uint8)
+    cs = np.zeros(max(1, count), dtype=np.uint64)
+    dp = (C.c_void_p * max(1, count))(*[d.ctypes.data if d.size else None for d in ds])
+    cp = (C.c_void_p * max(1, count))(*[o.ctypes.data for o in outs])
+    check(_lib.lib().vds_ec_block_pack_deflate_host_batch(
+        count, dp, dl.ctypes.data_as(_lib.u64p), ids.ctypes.data, keys.ctypes.data, cp,
+        cc.ctypes.data_as(_lib.u64p), cs.ctypes.data_as(_lib.u64p)), "block_pack_deflate_host_batch")
+    return [(bytes(ids[o]), bytes(keys[o]), outs[o][:int(cs[o])].tobytes()) for o in range(count)]
+
+
 def block_pack_batch(datas: Sequence, level: int = 6) -> list:
     """save_block / client::save for a batch of blocks: per block (id, key,
     crypted) with id = SHA-256(data), key = SHA-256(AES(id, data)) and crypted

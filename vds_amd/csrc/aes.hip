@@ -17,7 +17,10 @@
 // 16).  A quad stops after its own last block: a wave runs as long as its
 // longest chain, and the host orders the chains longest first.
 // k_aes256_cbc_encrypt_batch_lane is the one-lane-a-chain form, kept for the
-// A/B behind VDS_EC_AES_ENC=lane.
+// A/B behind VDS_EC_AES_ENC=lane.  k_aes256_cbc_encrypt_batch<true>
+// is the gated instance (the pack chain's last launch: the lengths are the
+// deflate's, on the device); <false> compiles to the instructions the kernel
+// had before it was a template (profiles/deflate_batch/README.md).
 //
 // k_aes256_cbc_decrypt_batch: CBC decryption has no chain (block i needs
 // ciphertext blocks i and i - 1), so the batch is tiled: a workgroup of
@@ -57,8 +60,12 @@ __device__ __forceinline__ uint32_t padded_word(aes_gptr_u32 p, uint32_t sh, uin
   return v;
 }
 
+// kGated: the chain's length is min(m.len, lens[m.idx]) (device uint32_t: the
+// deflate's out_lens in the pack chain; the host ordered the chains by m.len,
+// the upper bound), and out_lens[m.idx] receives what it encrypts to.
+template <bool kGated>
 __global__ __launch_bounds__(64) void k_aes256_cbc_encrypt_batch(const AesEncMsg *msgs, uint32_t count, uint64_t keys,
-                                                                 uint64_t ivs) {
+                                                                 uint64_t ivs, uint64_t lens, uint64_t out_lens) {
   __shared__ uint32_t te0[256];
   for (uint32_t i = threadIdx.x; i < 256u; i += 64u) te0[i] = kAesDev.te0[i];
   __syncthreads();
@@ -73,7 +80,11 @@ __global__ __launch_bounds__(64) void k_aes256_cbc_encrypt_batch(const AesEncMsg
                                                                                      : kAesBlockIvWords[3];
   if (ivs) st = aes_get_word(ivs + 16ull * m.idx + 4u * c);
 
-  const uint32_t len = m.len;
+  uint32_t len = m.len;
+  if constexpr (kGated) {
+    len = min(len, reinterpret_cast<aes_gptr_u32>(lens)[m.idx]);
+    if (c == 0) reinterpret_cast<aes_gptr_w32>(out_lens)[m.idx] = (len / 16u + 1u) * 16u;
+  }
   const uint32_t sh = (uint32_t)(m.in & 3u);
   const aes_gptr_u32 p = reinterpret_cast<aes_gptr_u32>(m.in - sh);
   const uint64_t lim = len ? (uint64_t)len + sh : 0;
@@ -285,8 +296,18 @@ hipError_t launch_aes_encrypt_batch(const AesEncMsg *msgs, uint32_t count, const
                        reinterpret_cast<uint64_t>(keys), reinterpret_cast<uint64_t>(ivs));
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_aes256_cbc_encrypt_batch, dim3((count + kAesEncChainsPerWave - 1) / kAesEncChainsPerWave),
-                     dim3(64), 0, s, msgs, count, reinterpret_cast<uint64_t>(keys), reinterpret_cast<uint64_t>(ivs));
+  hipLaunchKernelGGL(k_aes256_cbc_encrypt_batch<false>, dim3((count + kAesEncChainsPerWave - 1) / kAesEncChainsPerWave),
+                     dim3(64), 0, s, msgs, count, reinterpret_cast<uint64_t>(keys), reinterpret_cast<uint64_t>(ivs),
+                     uint64_t(0), uint64_t(0));
+  return hipGetLastError();
+}
+
+hipError_t launch_aes_encrypt_gated_batch(const AesEncMsg *msgs, uint32_t count, const uint8_t *keys,
+                                          const uint8_t *ivs, const uint32_t *lens, uint32_t *out_lens, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_aes256_cbc_encrypt_batch<true>, dim3((count + kAesEncChainsPerWave - 1) / kAesEncChainsPerWave),
+                     dim3(64), 0, s, msgs, count, reinterpret_cast<uint64_t>(keys), reinterpret_cast<uint64_t>(ivs),
+                     reinterpret_cast<uint64_t>(lens), reinterpret_cast<uint64_t>(out_lens));
   return hipGetLastError();
 }
 

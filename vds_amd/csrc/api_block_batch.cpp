@@ -9,7 +9,11 @@
 // inflate.hip through api_inflate_batch.cpp -- and the gated name check;
 // dht_network_client.cpp:1297-1316), and the host forms through pinned staging
 // (vds_ec_block_pack_host_batch, vds_ec_aes256_cbc_decrypt_host_batch,
-// vds_ec_block_unpack_host_batch).  Deflate stays the caller's.
+// vds_ec_block_unpack_host_batch).  The pack with the deflate on the device
+// too is five launches (vds_ec_block_pack_deflate_batch_device: hash, encrypt,
+// hash, deflate -- deflate.hip through api_deflate_batch.cpp -- and the encrypt
+// gated by the deflated lengths; vds_ec_aes256_cbc_encrypt_gated_batch_device
+// is that last launch on its own).
 // (api_internal.hpp lists the host runtime's translation units.)
 #include "api_internal.hpp"
 
@@ -56,8 +60,10 @@ AesScratch &aes_scratch() {
 // counting sort where the block counts are small against the batch (16,384
 // bodies of up to 4097 blocks), else a comparison sort.  Then the table in one
 // ring slot and the launch.  (Validated; the device is ready.)
+// dev_lens: the gated form (launch_aes_encrypt_gated_batch) -- lens are then the upper bounds.
 int enqueue_encrypt(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, const uint8_t *keys,
-                    const uint8_t *ivs, uint8_t *const *outs, hipStream_t s) {
+                    const uint8_t *ivs, uint8_t *const *outs, hipStream_t s, const uint32_t *dev_lens = nullptr,
+                    uint32_t *dev_out_lens = nullptr) {
   AesScratch &sc = aes_scratch();
   sc.key.resize(count);
   sc.order.resize(count);
@@ -85,7 +91,10 @@ int enqueue_encrypt(uint32_t count, const uint8_t *const *ins, const uint64_t *l
     t[j] = AesEncMsg{reinterpret_cast<uintptr_t>(ins[o]), reinterpret_cast<uintptr_t>(outs[o]), (uint32_t)lens[o], o};
   }
   e = param_commit(slot, bytes, s);
-  if (e == hipSuccess) {
+  if (e == hipSuccess && dev_lens) {
+    e = launch_aes_encrypt_gated_batch(reinterpret_cast<const AesEncMsg *>(slot->d), count, keys, ivs, dev_lens,
+                                       dev_out_lens, s);
+  } else if (e == hipSuccess) {
     // (read per call: VDS_EC_AES_ENC=lane runs the one-lane-a-chain kernel, the A/B arm of DESIGN 3.8b)
     const char *arm = std::getenv("VDS_EC_AES_ENC");
     e = launch_aes_encrypt_batch(reinterpret_cast<const AesEncMsg *>(slot->d), count, keys, ivs, s,
@@ -237,6 +246,79 @@ int enqueue_pack(uint32_t count, const uint8_t *const *datas, const uint64_t *da
   ps->pending = hipEventRecord(ps->done, s) == hipSuccess;
   if (!ps->pending) (void)hipStreamSynchronize(s);
   if (!rc) rc = enqueue_encrypt(count, zipped, zipped_lens, keys, nullptr, crypted, s);
+  return rc;
+}
+
+int check_pack_deflate_args(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens, const uint8_t *ids,
+                            const uint8_t *keys, uint8_t *const *crypted, const uint64_t *crypted_caps, bool device) {
+  if (count >= (1u << 30)) return VDS_EC_EINVAL;
+  if (count == 0) return VDS_EC_OK;
+  if (!datas || !data_lens || !ids || !keys || !crypted || !crypted_caps) return VDS_EC_EINVAL;
+  if (device && ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(keys)) & 3u)) return VDS_EC_EINVAL;
+  for (uint32_t o = 0; o < count; ++o) {
+    if (data_lens[o] > 0xFFFFFFFFull || (data_lens[o] && !datas[o]) || !crypted[o]) return VDS_EC_EINVAL;
+    const uint64_t w = padded_size(vds_ec_deflate_bound(data_lens[o]));
+    if (w > 0xFFFFFFFFull || crypted_caps[o] < w) return VDS_EC_EINVAL;
+    if (overlap(datas[o], data_lens[o], crypted[o], crypted_caps[o])) return VDS_EC_EINVAL;
+  }
+  return VDS_EC_OK;
+}
+
+// client::save with the deflate on the device.  Block o has one slot of the
+// pack's scratch, max(padded_size(len), the deflate's bound) bytes rounded up
+// to 16: first AES(id, data), which the key's hash reads and nobody after it,
+// then -- behind that hash in stream order -- the deflated bytes, which the
+// last encrypt reads; the deflated lengths (a uint32_t a block) follow the
+// slots.  So the scratch is about one byte an input byte.  Its last reader is
+// the last launch.  (Validated; the device is ready.)
+int enqueue_pack_deflate(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens, uint8_t *ids,
+                         uint8_t *keys, uint8_t *const *crypted, uint32_t *crypted_lens, hipStream_t s) {
+  PackScratch *ps = pack_scratch();
+  if (!ps) return VDS_EC_ENODEV;
+  auto slot_size = [](uint64_t len) {
+    return (std::max<uint64_t>(padded_size(len), vds_ec_deflate_bound(len)) + 15) & ~15ull;
+  };
+  uint64_t slots_b = 0;
+  for (uint32_t o = 0; o < count; ++o) slots_b += slot_size(data_lens[o]);
+  const uint64_t need = slots_b + 4ull * count;
+  std::lock_guard<std::mutex> g(ps->mu);
+  if (!ps->done && hipEventCreateWithFlags(&ps->done, hipEventDisableTiming) != hipSuccess) return VDS_EC_ENODEV;
+  if (need > ps->cap) {
+    if (ps->pending) (void)hipEventSynchronize(ps->done);
+    ps->pending = false;
+    if (ps->d) (void)hipFree(ps->d);
+    ps->d = nullptr;
+    ps->cap = 0;
+    size_t cap = 1u << 20;
+    while (cap < need) cap *= 2;
+    if (hipMalloc(&ps->d, cap) != hipSuccess) return VDS_EC_ENOMEM;
+    ps->cap = cap;
+  }
+  if (ps->pending) {
+    const hipError_t e = hipStreamWaitEvent(s, ps->done, 0);
+    if (e != hipSuccess) return hip_status(e);
+  }
+  PackTables &t = pack_tables();
+  t.tmp.resize(count);
+  t.tmp_len.resize(count);
+  thread_local std::vector<uint64_t> zip_caps;
+  zip_caps.resize(count);
+  uint64_t at = 0;
+  for (uint32_t o = 0; o < count; ++o) {
+    t.tmp[o] = ps->d + at;
+    t.tmp_len[o] = padded_size(data_lens[o]);
+    zip_caps[o] = vds_ec_deflate_bound(data_lens[o]);
+    at += slot_size(data_lens[o]);
+  }
+  uint32_t *zip_lens = reinterpret_cast<uint32_t *>(ps->d + slots_b);
+  int rc = sha256_batch_device(count, datas, data_lens, ids, s);
+  if (!rc) rc = enqueue_encrypt(count, datas, data_lens, ids, nullptr, t.tmp.data(), s);
+  if (!rc) rc = sha256_batch_device(count, t.tmp.data(), t.tmp_len.data(), keys, s);
+  if (!rc) rc = enqueue_deflate(count, datas, data_lens, t.tmp.data(), zip_caps.data(), zip_lens, s);
+  if (!rc) rc = enqueue_encrypt(count, t.tmp.data(), zip_caps.data(), keys, nullptr, crypted, s, zip_lens, crypted_lens);
+  // (the scratch's last reader, also when a step failed behind an earlier one's launch)
+  ps->pending = hipEventRecord(ps->done, s) == hipSuccess;
+  if (!ps->pending) (void)hipStreamSynchronize(s);
   return rc;
 }
 
@@ -514,6 +596,107 @@ int block_pack_host_batch(uint32_t count, const uint8_t *const *datas, const uin
   return VDS_EC_OK;
 }
 
+int aes_encrypt_gated_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *max_lens,
+                                   const uint32_t *lens, const uint8_t *keys, const uint8_t *ivs, uint8_t *const *outs,
+                                   uint32_t *out_lens, hipStream_t s) {
+  int rc = check_cipher_args(count, ins, max_lens, keys, outs, padded_size);
+  if (rc || count == 0) return rc;
+  if (!lens || !out_lens || ((reinterpret_cast<uintptr_t>(lens) | reinterpret_cast<uintptr_t>(out_lens)) & 3u))
+    return VDS_EC_EINVAL;
+  if ((rc = device_ready())) return rc;
+  return enqueue_encrypt(count, ins, max_lens, keys, ivs, outs, s, lens, out_lens);
+}
+
+int block_pack_deflate_batch_device(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                    uint8_t *ids, uint8_t *keys, uint8_t *const *crypted, const uint64_t *crypted_caps,
+                                    uint32_t *crypted_lens, hipStream_t s) {
+  int rc = check_pack_deflate_args(count, datas, data_lens, ids, keys, crypted, crypted_caps, true);
+  if (rc || count == 0) return rc;
+  if (!crypted_lens || (reinterpret_cast<uintptr_t>(crypted_lens) & 3u)) return VDS_EC_EINVAL;
+  if ((rc = device_ready())) return rc;
+  return enqueue_pack_deflate(count, datas, data_lens, ids, keys, crypted, crypted_lens, s);
+}
+
+int block_pack_deflate_host_batch(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens, uint8_t *ids,
+                                  uint8_t *keys, uint8_t *const *crypted, const uint64_t *crypted_caps,
+                                  uint64_t *crypted_sizes) {
+  int rc = check_pack_deflate_args(count, datas, data_lens, ids, keys, crypted, crypted_caps, false);
+  if (rc) return rc;
+  if (count && !crypted_sizes) return VDS_EC_EINVAL;
+  if (count == 0) return VDS_EC_OK;
+  if ((rc = device_ready())) return rc;
+  SaveTempStage *st = save_temp_stage();
+  if (!st) return VDS_EC_ENODEV;
+  std::vector<uint64_t> d_off, c_off;
+  std::vector<const uint8_t *> d_datas;
+  std::vector<uint8_t *> d_crypted;
+  std::vector<Copy> parts;
+  for (uint32_t o0 = 0; o0 < count;) {
+    // The group: blocks o0 .. o1-1, at most 64 MiB each way.  Data at 16-byte
+    // aligned offsets of the input staging; in the output staging the bodies'
+    // capacities (whole cipher blocks: back to back), the ids, the keys, the
+    // bodies' sizes.
+    d_off.clear();
+    c_off.clear();
+    uint64_t in_b = 0, out_b = 0;
+    uint32_t o1 = o0;
+    while (o1 < count && o1 - o0 < kSaveTempGroupObjects) {
+      const uint64_t da = (in_b + 15) & ~15ull, w = padded_size(vds_ec_deflate_bound(data_lens[o1]));
+      if (o1 > o0 && (da + data_lens[o1] > kSaveTempGroupBytes || out_b + w > kSaveTempGroupBytes)) break;
+      d_off.push_back(da);
+      in_b = da + data_lens[o1];
+      c_off.push_back(out_b);
+      out_b += w;
+      ++o1;
+    }
+    const uint32_t cnt = o1 - o0;
+    const uint64_t id_off = out_b, key_off = id_off + 32ull * cnt, len_off = key_off + 32ull * cnt,
+                   back_b = len_off + 4ull * cnt;
+    if ((rc = st->reserve(std::max<uint64_t>(in_b, 64), back_b))) return rc;
+    parts.clear();
+    for (uint32_t j = 0; j < cnt; ++j) parts.push_back({st->h_in + d_off[j], datas[o0 + j], data_lens[o0 + j]});
+    parallel_copy(parts);
+    hipError_t e = in_b ? hipMemcpyAsync(st->d_in, st->h_in, in_b, hipMemcpyHostToDevice, st->stream) : hipSuccess;
+    if (e != hipSuccess) return hip_status(e);
+    auto drained = [&](int r) {
+      (void)hipStreamSynchronize(st->stream);
+      return r;
+    };
+    d_datas.resize(cnt);
+    d_crypted.resize(cnt);
+    for (uint32_t j = 0; j < cnt; ++j) {
+      d_datas[j] = st->d_in + d_off[j];
+      d_crypted[j] = st->d_out + c_off[j];
+    }
+    rc = enqueue_pack_deflate(cnt, d_datas.data(), data_lens + o0, st->d_out + id_off, st->d_out + key_off,
+                              d_crypted.data(), reinterpret_cast<uint32_t *>(st->d_out + len_off), st->stream);
+    if (rc) return drained(rc);
+    // ids, keys and sizes first: only the bodies' own bytes come back
+    e = hipMemcpyAsync(st->h_out + id_off, st->d_out + id_off, back_b - id_off, hipMemcpyDeviceToHost, st->stream);
+    if (e != hipSuccess) return drained(hip_status(e));
+    if ((rc = hip_status(hipStreamSynchronize(st->stream)))) return rc;
+    const uint32_t *dl = reinterpret_cast<const uint32_t *>(st->h_out + len_off);
+    uint64_t hi = 0;
+    for (uint32_t j = 0; j < cnt; ++j) {
+      if (dl[j] > crypted_caps[o0 + j]) return VDS_EC_EHIP;  // (cannot be: the stored form is the bound)
+      hi = std::max<uint64_t>(hi, c_off[j] + dl[j]);
+    }
+    e = hipMemcpyAsync(st->h_out, st->d_out, hi, hipMemcpyDeviceToHost, st->stream);
+    if (e != hipSuccess) return drained(hip_status(e));
+    if ((rc = hip_status(hipStreamSynchronize(st->stream)))) return rc;
+    parts.clear();
+    for (uint32_t j = 0; j < cnt; ++j) {
+      parts.push_back({crypted[o0 + j], st->h_out + c_off[j], dl[j]});
+      crypted_sizes[o0 + j] = dl[j];
+    }
+    parts.push_back({ids + 32ull * o0, st->h_out + id_off, 32ull * cnt});
+    parts.push_back({keys + 32ull * o0, st->h_out + key_off, 32ull * cnt});
+    parallel_copy(parts);
+    o0 = o1;
+  }
+  return VDS_EC_OK;
+}
+
 int aes_decrypt_host_batch(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, const uint8_t *keys,
                            const uint8_t *ivs, uint8_t *const *outs, uint64_t *out_lens, int32_t *statuses,
                            uint32_t *failed) {
@@ -647,6 +830,27 @@ int vds_ec_block_pack_host_batch(uint32_t count, const uint8_t *const *datas, co
                                  uint8_t *keys, uint8_t *const *crypted, uint64_t *crypted_sizes) {
   return vds_ec::api::block_pack_host_batch(count, datas, data_lens, zipped, zipped_lens, ids, keys, crypted,
                                             crypted_sizes);
+}
+
+int vds_ec_aes256_cbc_encrypt_gated_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *max_lens,
+                                                 const uint32_t *lens, const uint8_t *keys, const uint8_t *ivs,
+                                                 uint8_t *const *outs, uint32_t *out_lens, void *stream) {
+  return vds_ec::api::aes_encrypt_gated_batch_device(count, ins, max_lens, lens, keys, ivs, outs, out_lens,
+                                                     vds_ec::api::as_stream(stream));
+}
+
+int vds_ec_block_pack_deflate_batch_device(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                           uint8_t *ids, uint8_t *keys, uint8_t *const *crypted,
+                                           const uint64_t *crypted_caps, uint32_t *crypted_lens, void *stream) {
+  return vds_ec::api::block_pack_deflate_batch_device(count, datas, data_lens, ids, keys, crypted, crypted_caps,
+                                                      crypted_lens, vds_ec::api::as_stream(stream));
+}
+
+int vds_ec_block_pack_deflate_host_batch(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
+                                         uint8_t *ids, uint8_t *keys, uint8_t *const *crypted,
+                                         const uint64_t *crypted_caps, uint64_t *crypted_sizes) {
+  return vds_ec::api::block_pack_deflate_host_batch(count, datas, data_lens, ids, keys, crypted, crypted_caps,
+                                                    crypted_sizes);
 }
 
 int vds_ec_aes256_cbc_decrypt_host_batch(uint32_t count, const uint8_t *const *ins, const uint64_t *lens,

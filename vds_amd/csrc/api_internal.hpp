@@ -26,6 +26,8 @@
 //                       (decrypt, inflate, name check) and the host forms;
 //   api_inflate_batch.cpp  zlib streams of a batch inflated on the device, and
 //                       the host form;
+//   api_deflate_batch.cpp  buffers of a batch deflated on the device, and the
+//                       host form;
 //   api_host_batch.cpp  caller-pinned slabs, the multi-GPU host batches and
 //                       the stripe-range split.
 #pragma once
@@ -230,6 +232,13 @@ int check_inflate_args(uint32_t count, const uint8_t *const *ins, const uint64_t
 int enqueue_inflate(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, uint8_t *const *outs,
                     const uint64_t *out_caps, uint32_t *out_lens, int32_t *statuses, const uint32_t *in_lens,
                     const int32_t *gate, hipStream_t s);
+// Buffers deflated (api_deflate_batch.cpp, deflate.hip).  check_deflate_args:
+// everything vds_ec_deflate_batch_device rejects but out_lens.  enqueue_deflate:
+// validated arguments, the device ready.
+int check_deflate_args(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, uint8_t *const *outs,
+                       const uint64_t *out_caps);
+int enqueue_deflate(uint32_t count, const uint8_t *const *ins, const uint64_t *lens, uint8_t *const *outs,
+                    const uint64_t *out_caps, uint32_t *out_lens, hipStream_t s);
 int repair_batch_device(uint32_t k, uint32_t count, const uint16_t *nodes, const uint8_t *const *chunks,
                         const uint64_t *chunk_sizes, uint32_t nt, const uint16_t *targets, uint8_t *const *outs,
                         uint8_t *digests, const uint8_t *expected, uint8_t *verdicts, hipStream_t s);

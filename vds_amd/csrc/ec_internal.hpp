@@ -595,10 +595,17 @@ hipError_t launch_b64_encode_gated_batch(const B64EncMsg *msgs, const B64EncGate
 // AesEncMsg::idx; lane_chain: one lane a chain instead of one quad (the A/B arm).  And the tiled decrypt.
 hipError_t launch_aes_encrypt_batch(const AesEncMsg *msgs, uint32_t count, const uint8_t *keys, const uint8_t *ivs,
                                     hipStream_t s, bool lane_chain = false);
+// The gated encrypt: chain idx is the first min(lens[idx], AesEncMsg::len) bytes (lens: device, the host
+// ordered by the upper bound AesEncMsg::len), and out_lens[idx] (device) receives what they encrypt to.
+hipError_t launch_aes_encrypt_gated_batch(const AesEncMsg *msgs, uint32_t count, const uint8_t *keys,
+                                          const uint8_t *ivs, const uint32_t *lens, uint32_t *out_lens, hipStream_t s);
 hipError_t launch_aes_decrypt_batch(const AesDecLaunch &l, hipStream_t s);
 // The gated name check of the unpack chain (sha256.hip), and the inflate of a batch (inflate.hip).
 hipError_t launch_sha256_gated_batch(const ShaBatchGatedLaunch &g, hipStream_t s);
 hipError_t launch_inflate_batch(const InflateLaunch &l, hipStream_t s);
+// The deflate of a batch (deflate.hip): one wave a message, msgs (device table, longest first) in the
+// inflate's layout with cap at least the deflate's bound; out_lens: uint32_t a message, by idx.
+hipError_t launch_deflate_batch(const InflateMsg *msgs, uint32_t count, uint32_t *out_lens, hipStream_t s);
 // One message on the calling CPU thread (aes_host.cpp); the decrypt returns its status.
 void aes256_cbc_encrypt_host(const uint8_t key[32], const uint8_t iv[16], const uint8_t *in, uint64_t len,
                              uint8_t *out);
