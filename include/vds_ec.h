@@ -65,6 +65,9 @@ extern "C" {
 #define VDS_EC_EINFLATE_DATA (-20)  /* what zlib answers Z_DATA_ERROR or Z_NEED_DICT to                     */
 #define VDS_EC_EINFLATE_SHORT (-21) /* the input ends before the stream does; what it held has been delivered */
 #define VDS_EC_EINFLATE_SPACE (-22) /* the plaintext would pass the output's capacity                        */
+/* transaction-log blocks (vds_ec_txblock_*) */
+#define VDS_EC_ETX_FORM (-23) /* not the canonical form of a block: the caller's own parser decides         */
+#define VDS_EC_ETX_KEY (-24)  /* the writer's key id matches none of the given keys: the caller looks it up */
 
 /* ----------------------------------------------------------------- flags */
 /* write_padding = false in chunk_generator::write (chunk.h:79,273-278):
@@ -1136,6 +1139,116 @@ int vds_ec_block_pack_deflate_batch_device(uint32_t count, const uint8_t *const 
 int vds_ec_block_pack_deflate_host_batch(uint32_t count, const uint8_t *const *datas, const uint64_t *data_lens,
                                          uint8_t *ids, uint8_t *keys, uint8_t *const *crypted,
                                          const uint64_t *crypted_caps, uint64_t *crypted_sizes);
+
+/* ------------------------------------------------- RSA signature verification
+ * The public-key check of the transaction log: asymmetric_sign_verify::verify
+ * (hash::sha256(), key, sig, data) -- EVP_DigestVerify* with an RSA key
+ * (kernel/vds_crypto/asymmetriccrypto.cpp:488-537), RSASSA-PKCS1-v1_5 over
+ * SHA-256 -- behind transaction_block::validate (sync_process.cpp:283), the
+ * signed messages inside a block (transaction_log.cpp:803, :1203) and
+ * allocate_storage (websocket_api.cpp:667).  Public data only: nothing here is
+ * constant-time.
+ *
+ * vds_ec_rsa_key: a public key ready for Montgomery arithmetic, a fixed-size
+ * POD that is copied to the device as it stands.  limbs is 64 (moduli up to
+ * 2048 bits) or 128; R = 2^(32 limbs).                                       */
+#define VDS_EC_RSA_MAX_LIMBS 128
+typedef struct vds_ec_rsa_key {
+  uint32_t n[VDS_EC_RSA_MAX_LIMBS];  /* the modulus, little-endian 32-bit limbs, zero above its length */
+  uint32_t rr[VDS_EC_RSA_MAX_LIMBS]; /* R^2 mod n, likewise                                            */
+  uint32_t limbs;                    /* 64 or 128                                                      */
+  uint32_t n_bytes;                  /* the modulus length in bytes (RSA_size): no leading zero byte   */
+  uint32_t e;                        /* the public exponent, odd, >= 3                                 */
+  uint32_t n0inv;                    /* -n^-1 mod 2^32                                                 */
+} vds_ec_rsa_key;
+/* From the big-endian magnitudes as the caller holds them (leading zero bytes
+ * allowed; DER parsing stays with the caller).  VDS_EC_EINVAL for a null
+ * argument, an even modulus, a modulus under 512 or over 4096 bits, an even
+ * e, e < 3 or e >= 2^32.                                                      */
+int vds_ec_rsa_key_prepare(const uint8_t *n_be, uint64_t n_len, const uint8_t *e_be, uint64_t e_len,
+                           vds_ec_rsa_key *key);
+/* asymmetric_public_key::fingerprint() (asymmetriccrypto.cpp:657-681): the
+ * SHA-256 of BE32(7) "ssh-rsa" BE32(len e) e BE32(len n) n, each magnitude
+ * without leading zero bytes and with one 00 in front when its top nibble is 9
+ * or above (the reference's own rule: a top nibble of 8 gets none).  The
+ * writer's key id of a transaction block.  VDS_EC_EINVAL for a null argument
+ * or a zero magnitude.                                                        */
+int vds_ec_rsa_fingerprint(const uint8_t *n_be, uint64_t n_len, const uint8_t *e_be, uint64_t e_len, uint8_t *out);
+/* in^e mod n on the calling thread (no GPU, no OpenSSL): in and out are
+ * key->n_bytes big-endian bytes.  VDS_EC_EINVAL for a null argument, in_len
+ * other than key->n_bytes, a value >= n.                                      */
+int vds_ec_rsa_public_host(const vds_ec_rsa_key *key, const uint8_t *in, uint64_t in_len, uint8_t *out);
+/* The verdict of EVP_DigestVerify(SHA-256) on the calling thread: *verdict 1
+ * or 0.  0 for a signature whose length is not key->n_bytes or whose value is
+ * >= n; otherwise sig^e mod n is compared, whole, with
+ * 00 01 FF..FF 00 || DigestInfo(SHA-256) || SHA-256(msg): nothing is parsed
+ * out of the decrypted block.  VDS_EC_EINVAL for a null key or verdict, a
+ * null msg or sig with a non-zero length.                                     */
+int vds_ec_rsa_verify_sha256_host(const vds_ec_rsa_key *key, const uint8_t *msg, uint64_t len, const uint8_t *sig,
+                                  uint64_t sig_len, uint8_t *verdict);
+/* The raw operation for `count` items in one launch, one wave an item.  ins,
+ * in_lens, key_idx, outs: HOST arrays (device pointers, lengths, indices into
+ * keys); keys: HOST, nkeys prepared keys, copied through the pinned parameter
+ * ring with the tables; items under 64- and 128-limb keys may be mixed.
+ * outs[o] receives the n_bytes of item o's key; statuses (DEVICE, one byte an
+ * item) 0, or (uint8_t)VDS_EC_EINVAL for an in_lens[o] that is not n_bytes or
+ * a value >= n, and then outs[o] is left untouched.  Nothing synchronises.
+ * Validated before anything is enqueued and before the device is looked for:
+ * VDS_EC_EINVAL for null arrays or a null pointer with count > 0, key_idx[o]
+ * >= nkeys, a key that vds_ec_rsa_key_prepare would not have produced, count
+ * >= 2^30; count == 0 is VDS_EC_OK.  Only outs' and statuses' own bytes are
+ * written.                                                                    */
+int vds_ec_rsa_public_batch_device(uint32_t count, const uint8_t *const *ins, const uint64_t *in_lens,
+                                   const uint32_t *key_idx, const vds_ec_rsa_key *keys, uint32_t nkeys,
+                                   uint8_t *const *outs, uint8_t *statuses, void *stream);
+/* vds_ec_rsa_verify_sha256_host's verdict for `count` signatures in ONE launch
+ * from digests already on the device: digests + 32 o (DEVICE) is SHA-256 of
+ * message o, sigs / sig_lens / key_idx HOST arrays as above, verdicts (DEVICE,
+ * one byte an item) 1 or 0.  The decrypted block is compared in the kernel and
+ * never stored.  Validation as above.                                         */
+int vds_ec_rsa_verify_digest_batch_device(uint32_t count, const uint8_t *digests, const uint8_t *const *sigs,
+                                          const uint64_t *sig_lens, const uint32_t *key_idx,
+                                          const vds_ec_rsa_key *keys, uint32_t nkeys, uint8_t *verdicts, void *stream);
+/* vds_ec_sha256_batch_device over msgs / lens, then the launch above: two
+ * launches.  digests (DEVICE, 32 count bytes) receives the digests; null: the
+ * library's own scratch holds them.  Validation as both.                      */
+int vds_ec_rsa_verify_sha256_batch_device(uint32_t count, const uint8_t *const *msgs, const uint64_t *lens,
+                                          const uint8_t *const *sigs, const uint64_t *sig_lens,
+                                          const uint32_t *key_idx, const vds_ec_rsa_key *keys, uint32_t nkeys,
+                                          uint8_t *verdicts, uint8_t *digests, void *stream);
+/* A transaction-log block as transaction_block::create reads it
+ * (transaction_block.cpp:11-50; binary_serialize.cpp:13-66, 245-): BE32
+ * version, BE64 time, BE64 order number, the writer's key id, the set of
+ * ancestors (a count, then the buffers), the messages, the signature -- every
+ * buffer behind its write_number length.  Offsets are from the block's first
+ * byte; a buffer's offset is that of its first byte behind the length.        */
+typedef struct vds_ec_txblock {
+  uint64_t time_point, order_no;
+  uint64_t key_id_off, key_id_len;
+  uint64_t ancestors_off, ancestors_len; /* the whole set, its count included    */
+  uint64_t ancestors_count;
+  uint64_t messages_off, messages_len;
+  uint64_t signature_off, signature_len;
+  uint64_t signed_len; /* the prefix in front of the signature's length: what validate() signs */
+} vds_ec_txblock;
+/* validate() (transaction_block.cpp:102-117) verifies a RE-SERIALISATION of
+ * the parsed fields, so only a block whose re-serialisation is its own prefix
+ * is accepted: version 0x31564453, every number in its shortest form, the
+ * ancestors strictly ascending in const_data_buffer::operator< (size first,
+ * then bytes), nothing behind the signature, a time that to_time_t /
+ * from_time_t give back (below 2^63 / 10^9).  Anything else, truncation
+ * included, is VDS_EC_ETX_FORM; VDS_EC_EINVAL for a null argument.            */
+int vds_ec_txblock_parse(const uint8_t *data, uint64_t len, vds_ec_txblock *out);
+/* apply_message's check for a drained batch of records, HOST memory in and
+ * out: ids + 32 o = SHA-256 of block o (the record's id); statuses[o]
+ * VDS_EC_OK, VDS_EC_ETX_FORM, or VDS_EC_ETX_KEY where the writer's key id is
+ * none of fingerprints + 32 j (j < nkeys; the caller then walks
+ * node_add_transaction); verdicts[o] the signature's verdict under keys[j]
+ * where the status is VDS_EC_OK, else 0.  The blocks are staged once: one
+ * SHA-256 launch gives ids and prefix digests, one launch verifies.           */
+int vds_ec_txblock_validate_host_batch(uint32_t count, const uint8_t *const *blocks, const uint64_t *lens,
+                                       const vds_ec_rsa_key *keys, const uint8_t *fingerprints, uint32_t nkeys,
+                                       uint8_t *ids, uint8_t *verdicts, int32_t *statuses);
 
 /* ----------------------------------------------------------------- utilities */
 /* Fill `size` device bytes at dst with the splitmix64 stream of `seed`

@@ -35,6 +35,8 @@ ECRYPT_PADDING = -19
 EINFLATE_DATA = -20
 EINFLATE_SHORT = -21
 EINFLATE_SPACE = -22
+ETX_FORM = -23
+ETX_KEY = -24
 
 F_NO_TRAILER = 0x1
 F_CELLS = 0x2
@@ -59,6 +61,19 @@ class WsFrame(C.Structure):
     _fields_ = [("fin", C.c_uint8), ("rsv1", C.c_uint8), ("rsv2", C.c_uint8), ("rsv3", C.c_uint8),
                 ("opcode", C.c_uint8), ("masked", C.c_uint8), ("mask", C.c_uint8 * 4), ("header_len", C.c_uint32),
                 ("need", C.c_uint32), ("payload_len", C.c_uint64)]
+
+
+class RsaKey(C.Structure):
+    """vds_ec_rsa_key (include/vds_ec.h)."""
+    _fields_ = [("n", C.c_uint32 * 128), ("rr", C.c_uint32 * 128), ("limbs", C.c_uint32), ("n_bytes", C.c_uint32),
+                ("e", C.c_uint32), ("n0inv", C.c_uint32)]
+
+
+class TxBlock(C.Structure):
+    """vds_ec_txblock (include/vds_ec.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("time_point", "order_no", "key_id_off", "key_id_len", "ancestors_off",
+                                          "ancestors_len", "ancestors_count", "messages_off", "messages_len",
+                                          "signature_off", "signature_len", "signed_len")]
 
 
 i32p = C.POINTER(C.c_int32)
@@ -201,6 +216,20 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "vds_ec_block_unpack_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.c_void_p, C.c_void_p, vpp, u64p, u64p,
                                                  i32p, u32p]),
+    "vds_ec_rsa_key_prepare": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(RsaKey)]),
+    "vds_ec_rsa_fingerprint": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vds_ec_rsa_public_host": (C.c_int, [C.POINTER(RsaKey), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vds_ec_rsa_verify_sha256_host": (C.c_int, [C.POINTER(RsaKey), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                C.c_void_p]),
+    "vds_ec_rsa_public_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, u32p, C.POINTER(RsaKey), C.c_uint32, vpp,
+                                                 C.c_void_p, C.c_void_p]),
+    "vds_ec_rsa_verify_digest_batch_device": (C.c_int, [C.c_uint32, C.c_void_p, vpp, u64p, u32p, C.POINTER(RsaKey),
+                                                        C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vds_ec_rsa_verify_sha256_batch_device": (C.c_int, [C.c_uint32, vpp, u64p, vpp, u64p, u32p, C.POINTER(RsaKey),
+                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vds_ec_txblock_parse": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(TxBlock)]),
+    "vds_ec_txblock_validate_host_batch": (C.c_int, [C.c_uint32, vpp, u64p, C.POINTER(RsaKey), C.c_void_p, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, i32p]),
     "vds_ec_base64_decoded_size": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "vds_ec_base64_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "vds_ec_base64_encode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -31,14 +31,14 @@ LOCK = os.path.join(HERE, ".build.lock")
 SOURCES = ["ec_encode_16_20.hip", "ec_encode_32_40.hip", "ec_encode_32_64.hip", "ec_encode_batch_32_64.hip",
            "ec_encode_batch_32_40.hip", "ec_encode_batch_16_20.hip", "ec_restore_syn_32a.hip",
            "ec_restore_syn_32b.hip", "ec_restore_syn_16.hip", "ec_encode.hip", "ec_restore_syn.hip", "ec_generic.hip",
-           "ec_restore_bs.hip", "sha256.hip", "inflate.hip", "deflate.hip", "dgram.hip", "base64.hip", "aes.hip", "vds_ec_api.cpp", "api_batch.cpp",
+           "ec_restore_bs.hip", "sha256.hip", "rsa.hip", "inflate.hip", "deflate.hip", "dgram.hip", "base64.hip", "aes.hip", "vds_ec_api.cpp", "api_batch.cpp",
            "api_encode_batch.cpp", "api_save_temp_batch.cpp", "api_upload_batch.cpp", "api_ws_batch.cpp", "api_download_batch.cpp", "api_dgram_batch.cpp",
-           "api_block_batch.cpp", "api_inflate_batch.cpp", "api_deflate_batch.cpp", "api_host_batch.cpp", "api_param_ring.cpp",
-           "vds_ec_wire.cpp", "vds_ec_jit.cpp", "sha256_host.cpp", "aes_host.cpp", "inflate_host.cpp", "deflate_host.cpp"]
-HOST_ONLY = {"sha256_host.cpp", "aes_host.cpp", "inflate_host.cpp", "deflate_host.cpp"}
+           "api_block_batch.cpp", "api_inflate_batch.cpp", "api_deflate_batch.cpp", "api_rsa_batch.cpp", "api_host_batch.cpp", "api_param_ring.cpp",
+           "vds_ec_wire.cpp", "vds_ec_jit.cpp", "sha256_host.cpp", "aes_host.cpp", "inflate_host.cpp", "deflate_host.cpp", "rsa_host.cpp"]
+HOST_ONLY = {"sha256_host.cpp", "aes_host.cpp", "inflate_host.cpp", "deflate_host.cpp", "rsa_host.cpp"}
 HEADERS = ["bitslice.hpp", "gf_common.hpp", "ec_internal.hpp", "ec_device.hpp", "restore_syn.hpp", "xorprog.hpp",
            "ec_encode.hpp", "ec_encode_batch.hpp", "ec_restore_syn.hpp", "api_internal.hpp", "sha256_device.hpp",
-           "aes_tables.hpp", "aes_device.hpp", "inflate_common.hpp", "deflate_common.hpp", "vds_ec_jitc.cpp"]
+           "aes_tables.hpp", "aes_device.hpp", "inflate_common.hpp", "deflate_common.hpp", "rsa_common.hpp", "vds_ec_jitc.cpp"]
 # The device sources the run-time kernels are compiled from (vds_ec_jit.cpp,
 # hiprtc in the helper vds_ec_jitc), embedded in the helper as jit_embed.inc
 # (written into the build directory).

@@ -1679,3 +1679,141 @@ def block_unpack_batch(crypted: Sequence, keys: Sequence, ids: Sequence) -> list
             raise VdsEcError(_lib.ECORRUPT, f"block_unpack_batch: block {o}")
         res.append(data)
     return res
+
+
+def _mag(value) -> np.ndarray:
+    """A big-endian magnitude from an int or from bytes as they stand."""
+    if isinstance(value, int):
+        value = value.to_bytes(max(1, (value.bit_length() + 7) // 8), "big")
+    return _u8(value)
+
+
+def rsa_key_prepare(n, e) -> _lib.RsaKey:
+    """vds_ec_rsa_key_prepare: the public key (n, e) -- ints or big-endian
+    bytes -- ready for the Montgomery arithmetic of the host and the device."""
+    nb, eb = _mag(n), _mag(e)
+    key = _lib.RsaKey()
+    check(_lib.lib().vds_ec_rsa_key_prepare(nb.ctypes.data, nb.size, eb.ctypes.data, eb.size, C.byref(key)),
+          "rsa_key_prepare")
+    return key
+
+
+def rsa_fingerprint(n, e) -> bytes:
+    """vds_ec_rsa_fingerprint: asymmetric_public_key::fingerprint(), the
+    writer's key id of a transaction block."""
+    nb, eb = _mag(n), _mag(e)
+    out = np.empty(32, dtype=np.uint8)
+    check(_lib.lib().vds_ec_rsa_fingerprint(nb.ctypes.data, nb.size, eb.ctypes.data, eb.size, out.ctypes.data),
+          "rsa_fingerprint")
+    return out.tobytes()
+
+
+def rsa_public_host(key: _lib.RsaKey, data) -> bytes:
+    """vds_ec_rsa_public_host: data^e mod n as key.n_bytes big-endian bytes, on
+    the calling thread.  VDS_EC_EINVAL for another length or a value >= n."""
+    d = _u8(data)
+    out = np.empty(max(1, key.n_bytes), dtype=np.uint8)
+    check(_lib.lib().vds_ec_rsa_public_host(C.byref(key), d.ctypes.data if d.size else None, d.size, out.ctypes.data),
+          "rsa_public_host")
+    return out[:key.n_bytes].tobytes()
+
+
+def rsa_verify_sha256_host(key: _lib.RsaKey, msg, sig) -> bool:
+    """vds_ec_rsa_verify_sha256_host: EVP_DigestVerify(SHA-256)'s verdict on
+    the calling thread, no GPU and no OpenSSL."""
+    m, s = _u8(msg), _u8(sig)
+    v = C.c_uint8(0)
+    check(_lib.lib().vds_ec_rsa_verify_sha256_host(C.byref(key), m.ctypes.data if m.size else None, m.size,
+                                                   s.ctypes.data if s.size else None, s.size, C.byref(v)),
+          "rsa_verify_sha256_host")
+    return bool(v.value)
+
+
+def _rsa_keys(keys):
+    ks = list(keys)
+    return (_lib.RsaKey * max(1, len(ks)))(*ks), len(ks)
+
+
+def rsa_public_batch_device(ins, in_lens, key_idx, keys, outs, statuses, stream=None) -> None:
+    """vds_ec_rsa_public_batch_device: item o, in_lens[o] big-endian bytes at
+    the device pointer ins[o], raised to e modulo n of keys[key_idx[o]] into the
+    key's n_bytes at the device pointer outs[o]; statuses (device, one byte an
+    item): 0, or 0xFF (VDS_EC_EINVAL) and outs[o] untouched.  One launch."""
+    ip, op = _ptr_table(ins), _ptr_table(outs)
+    ln = np.ascontiguousarray(np.asarray(in_lens, dtype=np.uint64).reshape(-1))
+    ki = _u32(key_idx)
+    if not (ip.size == ln.size == op.size == ki.size):
+        raise VdsEcError(_lib.EINVAL, "rsa_public_batch: the arrays do not describe one batch")
+    ka, nk = _rsa_keys(keys)
+    check(_lib.lib().vds_ec_rsa_public_batch_device(
+        ln.size, ip.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p), ki.ctypes.data_as(_lib.u32p), ka, nk,
+        op.ctypes.data_as(_lib.vpp), _dev_ptr(statuses), _stream_ptr(stream)), "rsa_public_batch_device")
+
+
+def rsa_verify_digest_batch_device(digests, sigs, sig_lens, key_idx, keys, verdicts, stream=None) -> None:
+    """vds_ec_rsa_verify_digest_batch_device: the verdict (device, one byte an
+    item, 1 or 0) of signature o -- sig_lens[o] bytes at the device pointer
+    sigs[o] -- over the SHA-256 digest at digests + 32 o (device) under
+    keys[key_idx[o]].  One launch."""
+    sp = _ptr_table(sigs)
+    ln = np.ascontiguousarray(np.asarray(sig_lens, dtype=np.uint64).reshape(-1))
+    ki = _u32(key_idx)
+    if not (sp.size == ln.size == ki.size):
+        raise VdsEcError(_lib.EINVAL, "rsa_verify_digest_batch: the arrays do not describe one batch")
+    ka, nk = _rsa_keys(keys)
+    check(_lib.lib().vds_ec_rsa_verify_digest_batch_device(
+        ln.size, _dev_ptr(digests), sp.ctypes.data_as(_lib.vpp), ln.ctypes.data_as(_lib.u64p),
+        ki.ctypes.data_as(_lib.u32p), ka, nk, _dev_ptr(verdicts), _stream_ptr(stream)),
+        "rsa_verify_digest_batch_device")
+
+
+def rsa_verify_sha256_batch_device(msgs, lens, sigs, sig_lens, key_idx, keys, verdicts, digests=None,
+                                   stream=None) -> None:
+    """vds_ec_rsa_verify_sha256_batch_device: the batched SHA-256 of the device
+    messages (msgs, lens), then the launch above; digests (device, 32 bytes an
+    item) receives the digests unless None."""
+    mp, sp = _ptr_table(msgs), _ptr_table(sigs)
+    ml = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(sig_lens, dtype=np.uint64).reshape(-1))
+    ki = _u32(key_idx)
+    if not (mp.size == ml.size == sp.size == ln.size == ki.size):
+        raise VdsEcError(_lib.EINVAL, "rsa_verify_sha256_batch: the arrays do not describe one batch")
+    ka, nk = _rsa_keys(keys)
+    check(_lib.lib().vds_ec_rsa_verify_sha256_batch_device(
+        ln.size, mp.ctypes.data_as(_lib.vpp), ml.ctypes.data_as(_lib.u64p), sp.ctypes.data_as(_lib.vpp),
+        ln.ctypes.data_as(_lib.u64p), ki.ctypes.data_as(_lib.u32p), ka, nk, _dev_ptr(verdicts), _dev_ptr(digests),
+        _stream_ptr(stream)), "rsa_verify_sha256_batch_device")
+
+
+def txblock_parse(data) -> tuple:
+    """vds_ec_txblock_parse -> (status, fields): VDS_EC_OK and the block's
+    fields (a dict of vds_ec_txblock's members), or VDS_EC_ETX_FORM and None."""
+    d = _u8(data)
+    b = _lib.TxBlock()
+    st = _lib.lib().vds_ec_txblock_parse(d.ctypes.data if d.size else None, d.size, C.byref(b))
+    if st == _lib.EINVAL and d.size == 0:  # (no bytes at all: no pointer to give)
+        st = _lib.ETX_FORM
+    if st not in (_lib.OK, _lib.ETX_FORM):
+        check(st, "txblock_parse")
+    return int(st), ({f: int(getattr(b, f)) for f, _ in _lib.TxBlock._fields_} if st == _lib.OK else None)
+
+
+def txblock_validate_host_batch(blocks: Sequence, keys, fingerprints: Sequence) -> list:
+    """vds_ec_txblock_validate_host_batch: per block (id, status, verdict) --
+    apply_message's check of a drained batch of transaction-log records (host
+    bytes) under the prepared keys and their fingerprints, on the device."""
+    bs = [_u8(b) for b in blocks]
+    count = len(bs)
+    ka, nk = _rsa_keys(keys)
+    fp = np.ascontiguousarray(np.frombuffer(b"".join(bytes(f) for f in fingerprints), dtype=np.uint8))
+    if fp.size != 32 * nk:
+        raise VdsEcError(_lib.EINVAL, "txblock_validate_host_batch: one fingerprint of 32 bytes per key")
+    ln = np.asarray([b.size for b in bs] or [0], dtype=np.uint64)
+    ids = np.zeros((max(1, count), 32), dtype=np.uint8)
+    ver = np.zeros(max(1, count), dtype=np.uint8)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    bp = (C.c_void_p * max(1, count))(*[b.ctypes.data if b.size else None for b in bs])
+    check(_lib.lib().vds_ec_txblock_validate_host_batch(
+        count, bp, ln.ctypes.data_as(_lib.u64p), ka, fp.ctypes.data if nk else None, nk, ids.ctypes.data,
+        ver.ctypes.data, st.ctypes.data_as(_lib.i32p)), "txblock_validate_host_batch")
+    return [(bytes(ids[o]), int(st[o]), int(ver[o])) for o in range(count)]

@@ -15,7 +15,7 @@ using namespace vds_ec::api;
 namespace vds_ec {
 namespace api {
 
-constexpr int kVersion = 102;  // 0.1.2: file blocks unpacked (vds_ec_inflate_*, vds_ec_block_unpack_*)
+constexpr int kVersion = 103;  // 0.1.3: RSA signatures verified (vds_ec_rsa_*, vds_ec_txblock_*)
 
 
 int hip_status(hipError_t e) {
@@ -1027,6 +1027,8 @@ const char *vds_ec_strerror(int status) {
     case VDS_EC_EINFLATE_DATA: return "inflate failed";
     case VDS_EC_EINFLATE_SHORT: return "inflate: the input ends before the stream does";
     case VDS_EC_EINFLATE_SPACE: return "inflate: the output's capacity is too small";
+    case VDS_EC_ETX_FORM: return "not the canonical form of a transaction block";
+    case VDS_EC_ETX_KEY: return "the block's writer is none of the given keys";
     default: return "unknown vds_ec status";
   }
 }
